@@ -10,15 +10,19 @@ offline).  One "step" = one whole batch of images: 20 UNet calls + sampler arith
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events on the launch stream
-(crg_profile_begin/end) around one extra, un-timed step; `cpu_baseline` times the CPU oracle
-(oracle/ref_cpu.py, "port") on a bounded sample of the same workload on the host cores (rank 0, N=1).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (its `ms_per_step` is
+one timed step); `--dump-outputs DIR` also writes what the last timed step computed, as DIR/<name>.npy.  `--full` adds what
+the headline figure does not need, after the timed region: `roofline`, measured live with HIP events on the launch stream
+(crg_profile_begin/end) around one extra, un-timed step; `cpu_baseline`, the CPU oracle (oracle/ref_cpu.py, "port") timed
+on a bounded sample of the same workload on the host cores (rank 0, N=1); and (N=1) the SDXL 1024x1024 extra workload.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 # multi-process GPU work on this pool needs dmabuf IPC (RCCL otherwise fails with hipIpcGetMemHandle: invalid argument); the variable is
 # exported by the image already - set here as well so that a bare `python -m torch.distributed.run ... bench.py` cannot miss it
@@ -33,6 +37,7 @@ FLOPS_UNET_PER_SAMPLE = 803.25e9   # SD1.5 UNet call per latent sample, L=64 (SU
 FLOPS_VAE_DECODE = 2514.5e9        # SD1.5 VAE decode per image, L=64
 PEAK_BF16_TFLOPS = 2500.0          # dense bf16 MFMA peak, MI355X_MICROARCH.md "Chip-level parameters"
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 63 * 10**6            # --dump-outputs: bytes of array data in all (under 64 MB with the .npy headers)
 
 
 def main():
@@ -57,10 +62,17 @@ def main():
     ap.add_argument("--unet-fp32", action="store_true",
                     help="extra line: the fp32-class UNet (fp32 activations, split-bf16 x3 MFMA) - the configuration whose 20-step trajectory "
                          "stays within 1e-3 of the fp32 CPU reference end to end (tests/test_hip_models.py::test_c1_sd15_full_20_step_trajectory)")
+    ap.add_argument("--full", action="store_true",
+                    help="headline workload: after the timed steps also measure the roofline / per-kernel figures, the CPU baseline and (N = 1) "
+                         "the extra SDXL 1024x1024 workload; the --no-* options below drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="headline workload: write what the last timed step computed (decoded images, "
+                                                          "rank 0's final latents) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra SDXL 1024x1024 measurement attached to the headline line (N = 1 only)")
     ap.add_argument("--no-roofline", action="store_true")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload != "sd15":
+        raise SystemExit("--dump-outputs covers the headline workload (--workload sd15) only")
     if a.half == "f16":
         os.environ["CRG_HALF"] = "f16"  # read by cremage_amd._lib at import: selects libcrg_hip_f16.so and torch.float16 activations
 
@@ -93,11 +105,13 @@ def main():
     c = torch.stack([synth_input(f"bench.c{first + i}", (77, 768), 7) for i in range(b)]).to(dev)
     uc = synth_input("bench.uc", (1, 77, 768), 7).expand(b, -1, -1).contiguous().to(dev)
     gens = [torch.Generator(device=dev).manual_seed(D.image_seed(42, first + i)) for i in range(b)]
+    last = {}
 
     def step(gather=True):
         # P.txt2img draws the initial latents and the ancestral noise of image i from its own generator (seed + global image index),
         # the whole trajectory's noise up front (pipeline.trajectory_noise_sampler) - the library's default path, not a bench shortcut
-        images, _ = P.txt2img(ldm, c, uc, steps=a.sampler_steps, sampler=a.sampler, cfg_scale=7.5, height=512, width=512, generators=gens)
+        images, last["latents"] = P.txt2img(ldm, c, uc, steps=a.sampler_steps, sampler=a.sampler, cfg_scale=7.5, height=512, width=512,
+                                            generators=gens)
         # gather=False: the rank-0-only profiling steps behind the timed region must not enter a collective the other ranks never join
         return D.all_gather_batch(images) if gather else images
 
@@ -112,6 +126,8 @@ def main():
     D.barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0, dev)
     assert out.shape == (world * b, 3, 512, 512) and torch.isfinite(out).all()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"images": out, "latents": last["latents"]})
 
     n_images = world * b * a.steps
     value = n_images / dt
@@ -145,7 +161,7 @@ def main():
     }
 
     # ---- roofline of the dominant kernel: HIP events on the launch stream, one extra un-timed step ----
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         ldm.model.enable_hip_graph(False)  # per-launch HIP events need eager launches (a replay is one opaque node list)
         step(gather=False)
         with ops.profile(local) as prof:
@@ -159,7 +175,7 @@ def main():
             for k, v in fam.items() if v["launches"] and v["ms"] > 0}
 
     # ---- CPU baseline: the oracle ("port") on a bounded sample of the same workload ----
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import ref_cpu as R
         usd = {k: v.detach().float().cpu() for k, v in ldm.model.diffusion_model.state_dict().items()}
         vsd = {k: v.detach().float().cpu() for k, v in ldm.first_stage_model.state_dict().items()}
@@ -178,7 +194,7 @@ def main():
                                "sample": f"1 UNet call (B=2 = one image x CFG, 64x64 latent, fp32) = {t_unet:.2f} s and 1 VAE decode = "
                                          f"{t_dec:.2f} s on the host; images/s = 1 / (20 * t_unet + t_dec)"}
     # ---- the 1024x1024 workload (BASELINE.json configs[2], north_star "512x512 and 1024x1024") in the same record ----
-    if rank == 0 and world == 1 and not a.no_extra and a.half == "bf16" and not a.unet_fp32:
+    if rank == 0 and world == 1 and a.full and not a.no_extra and a.half == "bf16" and not a.unet_fp32:
         t_extra = time.time()
         try:
             import gc
@@ -194,6 +210,19 @@ def main():
         print(json.dumps(res))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor of `arrays` as <path>/<name>.npy in float32.  Above DUMP_BYTES in all, every array keeps the same share of
+    its flattened elements, drawn with a fixed seed: the same elements on every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(x.nbytes for x in arrs.values())
+    for k, x in arrs.items():
+        if total > DUMP_BYTES:
+            keep = x.size * DUMP_BYTES // total
+            x = x.reshape(-1)[np.sort(np.random.RandomState(0).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), x)
 
 
 # End-to-end error of each UNet operand type against the fp32 CPU reference: full-size C1 (SD1.5 512x512, 20-step Euler, CFG 7.5, one

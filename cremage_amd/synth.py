@@ -15,6 +15,7 @@ Scales: matrices/conv kernels ~ N(0, 1/fan_in); biases ~ 0.05*N(0,1); 1-D "weigh
 (`zero_module`, openaimodel.py:233-235,755; attention.py:1002) are re-randomised like
 any other, otherwise every block would be an identity and parity vacuous.
 """
+import concurrent.futures as cf
 import zlib
 
 import numpy as np
@@ -53,11 +54,14 @@ def synth_tensor(name: str, shape, seed: int, kind: str = "auto") -> torch.Tenso
 
 @torch.no_grad()
 def synth_fill_(module: torch.nn.Module, seed: int, prefix: str = "") -> torch.nn.Module:
-    """Overwrite every >=1-D parameter of `module` in place (0-D LoRA alphas are kept)."""
-    for name, p in module.named_parameters():
-        if p.ndim == 0 or "_lora_" in name:
-            continue
-        p.copy_(synth_tensor(prefix + name, p.shape, seed).to(p.dtype))
+    """Overwrite every >=1-D parameter of `module` in place (0-D LoRA alphas are kept).  The tensors are drawn on a thread pool
+    (numpy's generator releases the GIL; serially the SD1.5 UNet alone takes ~20 s): each depends on its name and seed only, so
+    the weights are the same as a serial fill's."""
+    params = [(name, p) for name, p in module.named_parameters() if p.ndim > 0 and "_lora_" not in name]
+    with cf.ThreadPoolExecutor(max_workers=max(1, min(16, torch.get_num_threads()))) as ex:
+        drawn = ex.map(lambda item: synth_tensor(prefix + item[0], item[1].shape, seed), params)
+        for (_, p), x in zip(params, drawn):
+            p.copy_(x.to(p.dtype))  # on this thread: grad mode is per thread, and no_grad holds here only
     return module
 
 

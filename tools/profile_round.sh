@@ -10,7 +10,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra --no-graph"
+BENCH="python3 $ROOT/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extra --no-graph"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_stats" -o runc -- $BENCH > "$OUT/${TAG}_stats.log" 2>&1
 echo "stats pass done"

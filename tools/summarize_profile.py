@@ -92,7 +92,7 @@ def main():
     ap.add_argument("--fetch")
     ap.add_argument("--write")
     ap.add_argument("--bench-json")
-    ap.add_argument("--cmd", default="python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline")
+    ap.add_argument("--cmd", default="python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline")
     a = ap.parse_args()
     rows = list(csv.DictReader(open(a.stats)))
     dm = demangle([r["Name"] for r in rows])
