@@ -228,6 +228,32 @@ __global__ __launch_bounds__(256) void transpose_kernel(const ST* __restrict__ s
   }
 }
 
+// cat([a, b], dim 1) of two NCHW tensors -> one NHWC tensor, the concat folded into the transpose: a [N][Ca][HW], b [N][Cb][HW],
+// dst [N][HW][Ca + Cb].  Channel rows below Ca come from a, the rest from b (same 32x32 tile walk as transpose_kernel).
+template <typename ST, typename DT>
+__global__ __launch_bounds__(256) void transpose_cat_kernel(const ST* __restrict__ a, const ST* __restrict__ b, DT* __restrict__ dst, int Ca,
+                                                            int Cb, int HW) {
+  __shared__ float tile[32][33];
+  const int n = blockIdx.z;
+  const int C = Ca + Cb;
+  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;  // r: channel, c: pixel
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const ST* sa = a + (long)n * Ca * HW;
+  const ST* sb = b + (long)n * Cb * HW;
+  DT* d = dst + (long)n * C * HW;
+  for (int i = ty; i < 32; i += 8) {
+    const int rr = r0 + i, cc = c0 + tx;
+    float v = 0.f;
+    if (rr < C && cc < HW) v = rr < Ca ? (float)sa[(long)rr * HW + cc] : (float)sb[(long)(rr - Ca) * HW + cc];
+    tile[i][tx] = v;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int cc = c0 + i, rr = r0 + tx;
+    if (rr < C && cc < HW) d[(long)cc * C + rr] = (DT)tile[tx][i];
+  }
+}
+
 template <typename ST, typename DT>
 __global__ void affine_cast_kernel(const ST* __restrict__ x, DT* __restrict__ y, long n, float a, float b, float lo, float hi) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -274,7 +300,7 @@ extern "C" int crg_conv_small(crg_ctx* ctx, void* stream, const void* x, const f
                               int N, int H, int W, int Cin, int Cout, int ksize, int x_dtype, int y_dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_small: empty problem");
-  CRG_REQUIRE(ctx, Cin <= 8 || Cout <= 8, "conv_small: needs Cin <= 8 or Cout <= 8 (Cin=%d Cout=%d)", Cin, Cout);
+  CRG_REQUIRE(ctx, Cin <= 9 || Cout <= 8, "conv_small: needs Cin <= 9 or Cout <= 8 (Cin=%d Cout=%d)", Cin, Cout);
   hipStream_t st = (hipStream_t)stream;
   const int ks = ksize;
   CRG_REQUIRE(ctx, ks == 1 || ks == 3, "conv_small: ksize %d unsupported", ks);
@@ -308,13 +334,17 @@ extern "C" int crg_conv_small(crg_ctx* ctx, void* stream, const void* x, const f
     });
   } else {
     CRG_REQUIRE(ctx, Cout % 8 == 0, "conv_small: Cout=%d must be a multiple of 8 when Cin <= 8", Cout);
-    CRG_REQUIRE(ctx, Cin == 3 || Cin == 4 || Cin == 8, "conv_small: Cin=%d unsupported on the thin-input path (3, 4 or 8)", Cin);
+    CRG_REQUIRE(ctx, Cin == 3 || Cin == 4 || Cin == 8 || Cin == 9, "conv_small: Cin=%d unsupported on the thin-input path (3, 4, 8 or 9)",
+                Cin);
     const size_t lds = (size_t)ks * ks * Cin * Cout * sizeof(float);
     CRG_REQUIRE(ctx, lds <= 160 * 1024, "conv_small: Cout=%d too large for the LDS weight image", Cout);
     rc = by_dtype2(ctx, x_dtype, y_dtype, "conv_small", [&](auto* xs, auto* ys) {
       using XT = std::remove_const_t<std::remove_pointer_t<decltype(xs)>>;
       using YT = std::remove_pointer_t<decltype(ys)>;
-      const bool quad = W % 4 == 0 && Cin <= 4;  // 4 pixels per thread (8-channel inputs would need 32 more registers: one pixel)
+      // 4 pixels per thread (8-channel inputs would need 32 more registers: one pixel).  The 9-channel conv_in of the inpainting
+      // UNet (4 latent + 1 mask + 4 masked-image channels) keeps a 101 KiB weight image, i.e. one block per CU and one wave per SIMD:
+      // there the registers are free and the four pixels' independent FMA chains are the only latency hiding left.
+      const bool quad = W % 4 == 0 && (Cin <= 4 || Cin == 9);
       const dim3 grid(grid_resident((long)N * H * (quad ? W / 4 : W) * (Cout / 8), lds));
       auto go = [&](auto kern) {
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -323,10 +353,12 @@ extern "C" int crg_conv_small(crg_ctx* ctx, void* stream, const void* x, const f
       if (ks == 3) {
         if (Cin == 3) quad ? go(conv_small_cin_kernel<XT, YT, 3, 4, 3>) : go(conv_small_cin_kernel<XT, YT, 3, 1, 3>);
         else if (Cin == 4) quad ? go(conv_small_cin_kernel<XT, YT, 4, 4, 3>) : go(conv_small_cin_kernel<XT, YT, 4, 1, 3>);
+        else if (Cin == 9) quad ? go(conv_small_cin_kernel<XT, YT, 9, 4, 3>) : go(conv_small_cin_kernel<XT, YT, 9, 1, 3>);
         else go(conv_small_cin_kernel<XT, YT, 8, 1, 3>);
       } else {
         if (Cin == 3) quad ? go(conv_small_cin_kernel<XT, YT, 3, 4, 1>) : go(conv_small_cin_kernel<XT, YT, 3, 1, 1>);
         else if (Cin == 4) quad ? go(conv_small_cin_kernel<XT, YT, 4, 4, 1>) : go(conv_small_cin_kernel<XT, YT, 4, 1, 1>);
+        else if (Cin == 9) go(conv_small_cin_kernel<XT, YT, 9, 1, 1>);
         else go(conv_small_cin_kernel<XT, YT, 8, 1, 1>);
       }
       return 0;
@@ -396,6 +428,25 @@ extern "C" int crg_nhwc_to_nchw(crg_ctx* ctx, void* stream, const void* src, voi
                                 int dst_dtype) {
   if (!ctx) return -22;
   return transpose_impl(ctx, stream, src, dst, N, HW, C, src_dtype, dst_dtype, "nhwc_to_nchw");
+}
+
+extern "C" int crg_nchw2_to_nhwc(crg_ctx* ctx, void* stream, const void* src_a, const void* src_b, void* dst, int N, int Ca, int Cb,
+                                 int HW, int src_dtype, int dst_dtype) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, N > 0 && Ca > 0 && Cb > 0 && HW > 0 && src_a && src_b && dst, "nchw2_to_nhwc: empty");
+  hipStream_t st = (hipStream_t)stream;
+  const double elems = (double)N * (Ca + Cb) * HW;
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, 0.0, elems * (crg_dtype_size(src_dtype) + crg_dtype_size(dst_dtype)));
+  dim3 grid((HW + 31) / 32, (Ca + Cb + 31) / 32, N);
+  int rc = by_dtype2(ctx, src_dtype, dst_dtype, "nchw2_to_nhwc", [&](auto* xs, auto* ys) {
+    using ST = std::remove_const_t<std::remove_pointer_t<decltype(xs)>>;
+    using DT = std::remove_pointer_t<decltype(ys)>;
+    hipLaunchKernelGGL((transpose_cat_kernel<ST, DT>), grid, dim3(256), 0, st, (const ST*)src_a, (const ST*)src_b, (DT*)dst, Ca, Cb, HW);
+    return 0;
+  });
+  if (rc) return rc;
+  CRG_CHECK_LAUNCH(ctx, "nchw2_to_nhwc");
+  return 0;
 }
 
 extern "C" int crg_affine_cast(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, float lo,
@@ -502,6 +553,41 @@ extern "C" int crg_cfg_euler_step(crg_ctx* ctx, void* stream, void* x, const voi
   hipLaunchKernelGGL(cfg_euler_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, (float*)x, (const float*)eps, (const float*)noise, (long)n,
                      sigma, dt, cfg_scale, noise_scale);
   CRG_CHECK_LAUNCH(ctx, "cfg_euler_step");
+  return 0;
+}
+
+namespace {
+// One fused DDIM step (see include/crg_hip.h): p_sample_ddim's elementwise chain, one fp32 rounding per operation in the reference's
+// order (no FMA contraction).  The per-step scalars arrive already rounded to fp32, as torch.full((b,1,1,1), table[index]) does.
+__global__ __launch_bounds__(256) void cfg_ddim_step_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                                            const float* __restrict__ noise, long n, float cfg, float sqrt_one_minus_a,
+                                                            float sqrt_a, float sqrt_a_prev, float dir_coef, float sigma) {
+#pragma clang fp contract(off)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float eu = eps[i];
+    const float e = eu + cfg * (eps[n + i] - eu);
+    const float xv = x[i];
+    const float x0 = (xv - sqrt_one_minus_a * e) / sqrt_a;
+    const float dir = dir_coef * e;
+    float xn = sqrt_a_prev * x0 + dir;
+    if (noise) xn = xn + sigma * noise[i];
+    x[i] = xn;
+  }
+}
+}  // namespace
+
+extern "C" int crg_cfg_ddim_step(crg_ctx* ctx, void* stream, void* x, const void* eps, const void* noise, int64_t n, float cfg_scale,
+                                 float sqrt_one_minus_a, float sqrt_a, float sqrt_a_prev, float dir_coef, float sigma) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, n > 0 && x && eps, "cfg_ddim_step: empty input");
+  CRG_REQUIRE(ctx, sqrt_a > 0.f, "cfg_ddim_step: sqrt(alpha) must be positive (got %g)", (double)sqrt_a);
+  CRG_REQUIRE(ctx, sigma == 0.f || noise, "cfg_ddim_step: sigma %g > 0 needs a noise tensor", (double)sigma);
+  hipStream_t st = (hipStream_t)stream;
+  if (sigma == 0.f) noise = nullptr;  // eta = 0: the noise term is sigma * z = 0, nothing to read
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, 10.0 * n, 4.0 * n * (noise ? 5 : 4));
+  hipLaunchKernelGGL(cfg_ddim_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, (float*)x, (const float*)eps, (const float*)noise, (long)n,
+                     cfg_scale, sqrt_one_minus_a, sqrt_a, sqrt_a_prev, dir_coef, sigma);
+  CRG_CHECK_LAUNCH(ctx, "cfg_ddim_step");
   return 0;
 }
 

@@ -99,7 +99,8 @@ class GraphedModule:
         rows = {k: v._crg_time_rows for k, v in dyn.items() if getattr(v, "_crg_time_rows", None) is not None}
         key = (self._sig(x), dup, tuple((k, self._sig(v), id(rows[k][0]) if k in rows else None, self._sig(rows[k][1]) if k in rows else None)
                                         for k, v in sorted(dyn.items())),
-               tuple((k, id(v), v._version, self._sig(v)) for k, v in sorted(consts.items())), tuple(sorted(other.items())))
+               tuple((k, id(v), v._version, self._sig(v), bool(getattr(v, "_crg_cfg_dup", False))) for k, v in sorted(consts.items())),
+               tuple(sorted(other.items())))
         if self.broken:
             return self.module(x, **kw)
         g = self._graphs.get(key)

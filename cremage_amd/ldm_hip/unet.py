@@ -369,15 +369,18 @@ class UNetModel(nn.Module):
             self.__dict__["_crg_cfg_split"] = r
         return r
 
-    def _input_blocks(self, x, cdt, emb, context, cfg_dup: bool):
+    def _input_blocks(self, x, cdt, emb, context, cfg_dup: bool, c_concat=None):
         """The encoder half (openaimodel.py:804-806): returns (h, hs).  With `cfg_dup` - x is cat([x'] * 2) and the timesteps are
         doubled likewise, the caller's promise - everything before the first cross-attention runs on ONE half: both halves would
         compute the same values there (conv_in, the first ResBlock, GroupNorm + proj_in, LayerNorm + Q | K | V, the 64x64 self-attention,
-        its out-projection, LayerNorm + to_q)."""
+        its out-projection, LayerNorm + to_q).  `c_concat` (hybrid conditioning) enters conv_in through the input conversion; a
+        split then needs the same promise on it as well (ops.mark_cfg_dup(c_concat)), else the whole batch runs."""
+        if c_concat is not None and not getattr(c_concat, "_crg_cfg_dup", False):
+            cfg_dup = False
         split = self._cfg_split_index() if (cfg_dup and ops.CFG_SHARE and x.shape[0] % 2 == 0 and context is not None) else None
         hs = []
         if split is None:
-            h = ops.nchw_to_nhwc(x, cdt)
+            h = ops.nchw_to_nhwc(x, cdt, c_concat)
             for module in self.input_blocks:
                 h = module(h, emb, context)
                 hs.append(h)
@@ -385,7 +388,7 @@ class UNetModel(nn.Module):
         half = x.shape[0] // 2
         emb_h = emb[:half]
         emb_h._crg_emb_out = {k: v[:half] for k, v in emb._crg_emb_out.items()}
-        h = ops.nchw_to_nhwc(x[:half], cdt)
+        h = ops.nchw_to_nhwc(x[:half], cdt, c_concat[:half] if c_concat is not None else None)
         for i, module in enumerate(self.input_blocks):
             if i < split:
                 h = module(h, emb_h, context)
@@ -401,12 +404,16 @@ class UNetModel(nn.Module):
                 hs.append(h)
         return h, hs
 
-    def forward(self, x, timesteps=None, context=None, y=None, cfg_dup: bool = False, **kwargs):
+    def forward(self, x, timesteps=None, context=None, y=None, cfg_dup: bool = False, c_concat=None, **kwargs):
         """x [N, C, H, W] (any float dtype, NCHW) , timesteps [N] (may be fractional), context [N, T, D]
-        -> eps [N, C_out, H, W] in x.dtype (openaimodel.py:780-816).  `cfg_dup` (or ops.mark_cfg_dup(x)): see _input_blocks."""
+        -> eps [N, C_out, H, W] in x.dtype (openaimodel.py:780-816).  `cfg_dup` (or ops.mark_cfg_dup(x)): see _input_blocks.
+        `c_concat` [N, C_c, H, W] (hybrid conditioning, e.g. the inpainting model's mask + masked-image latents): the result equals
+        forward(cat([x, c_concat], dim 1)) - ddpm.py:1520-1523 - without building the concatenated tensor."""
         assert y is None, "must specify y if and only if the model is class-conditional"
+        if c_concat is not None and x.shape[1] + c_concat.shape[1] != self.in_channels:
+            raise ValueError(f"UNetModel: x {x.shape[1]} + c_concat {c_concat.shape[1]} channels, the model takes {self.in_channels}")
         cdt, emb, context = self._prologue(timesteps, context)
-        h, hs = self._input_blocks(x, cdt, emb, context, cfg_dup or getattr(x, "_crg_cfg_dup", False))
+        h, hs = self._input_blocks(x, cdt, emb, context, cfg_dup or getattr(x, "_crg_cfg_dup", False), c_concat)
         h = self.middle_block(h, emb, context)
         for module in self.output_blocks:
             h = module((h, hs.pop()), emb, context)

@@ -444,16 +444,29 @@ def time_rows_of(timesteps, owner):
     return tr[1] if (TIME_ROWS and tr is not None and tr[0] is owner) else None
 
 
-def nchw_to_nhwc(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """Contiguous NCHW tensor -> channels-last tensor of `dtype` (one transpose+cast kernel)."""
-    _need_cuda(x)
+def nchw_to_nhwc(x: torch.Tensor, dtype: torch.dtype, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Contiguous NCHW tensor -> channels-last tensor of `dtype` (one transpose+cast kernel).  `x2` [N, C2, H, W]: the result is
+    cat([x, x2], dim 1) (crg_nchw2_to_nhwc: the concat is folded into the same launch, no concatenated tensor is built)."""
+    _need_cuda(x, x2)
     n, c, hh, ww = x.shape
     if x.dtype not in (torch.float32, HALF):
         x = x.float()
     x = x.contiguous()
-    y = empty_image(n, c, hh, ww, dtype, x.device)
+    if x2 is None:
+        y = empty_image(n, c, hh, ww, dtype, x.device)
+        h = _h(x)
+        L.check(L.load().crg_nchw_to_nhwc(h, _st(), _p(x), _p(y), n, c, hh * ww, _act_dt(x), _DT[dtype]), h, "crg_nchw_to_nhwc")
+        return y
+    if x2.dim() != 4 or x2.shape[0] != n or tuple(x2.shape[2:]) != (hh, ww):
+        raise L.CrgError(f"nchw_to_nhwc: second source {tuple(x2.shape)} does not match {tuple(x.shape)} in batch and size")
+    if x2.dtype != x.dtype:
+        x2 = x2.to(x.dtype)
+    x2 = x2.contiguous()
+    c2 = x2.shape[1]
+    y = empty_image(n, c + c2, hh, ww, dtype, x.device)
     h = _h(x)
-    L.check(L.load().crg_nchw_to_nhwc(h, _st(), _p(x), _p(y), n, c, hh * ww, _act_dt(x), _DT[dtype]), h, "crg_nchw_to_nhwc")
+    L.check(L.load().crg_nchw2_to_nhwc(h, _st(), _p(x), _p(x2), _p(y), n, c, c2, hh * ww, _act_dt(x), _DT[dtype]), h,
+            "crg_nchw2_to_nhwc")
     return y
 
 
@@ -816,7 +829,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     hv, wv = (2 * hh, 2 * ww) if upsample2x else (hh, ww)
     ho = (hv + pt + pb - ks) // stride + 1
     wo = (wv + pl + pr - ks) // stride + 1
-    if cin <= 8 or (cout <= 8 and (cin % 8 != 0 or cin < 64)):
+    if cin <= 8 or (cin == 9 and cout % 8 == 0) or (cout <= 8 and (cin % 8 != 0 or cin < 64)):  # 9: the inpainting UNet's conv_in
         if x_lo is not None:
             raise L.CrgError("conv2d: thin-channel convs take the fp32 tensor, not split planes")
         if stride != 1 or upsample2x or x2 is not None or cvec is not None or residual is not None or gn is not None or (pt, pl, pb, pr) != (ks // 2,) * 4:
@@ -1053,6 +1066,25 @@ def cfg_euler_step_(x: torch.Tensor, eps2: torch.Tensor, noise: Optional[torch.T
     h = _h(x)
     L.check(L.load().crg_cfg_euler_step(h, _st(), _p(x), _p(eps2), _p(noise), x.numel(), float(sigma), float(dt), float(cfg_scale),
                                         float(noise_scale)), h, "crg_cfg_euler_step")
+    return _written(x)
+
+
+def cfg_ddim_step_(x: torch.Tensor, eps2: torch.Tensor, noise: Optional[torch.Tensor], cfg_scale: float, sqrt_one_minus_a: float,
+                   sqrt_a: float, sqrt_a_prev: float, dir_coef: float, sigma: float) -> torch.Tensor:
+    """In-place fused DDIM step (crg_cfg_ddim_step): x fp32 [b, ...], eps2 fp32 [2b, ...] (uncond half first), noise fp32 [b, ...]
+    (read only when sigma > 0).  The scalars are the fp32 values p_sample_ddim broadcasts (see include/crg_hip.h)."""
+    if sigma == 0.0:
+        noise = None
+    _need_cuda(x, eps2, noise)
+    if x.dtype != torch.float32 or eps2.dtype != torch.float32 or not x.is_contiguous() or not eps2.is_contiguous() \
+            or eps2.numel() != 2 * x.numel() or (noise is not None and (noise.dtype != torch.float32 or not noise.is_contiguous()
+                                                                         or noise.numel() != x.numel())):
+        raise L.CrgError("cfg_ddim_step_: contiguous fp32 x [b,...], eps [2b,...] and noise [b,...] expected")
+    if sigma != 0.0 and noise is None:
+        raise L.CrgError("cfg_ddim_step_: sigma > 0 needs a noise tensor")
+    h = _h(x)
+    L.check(L.load().crg_cfg_ddim_step(h, _st(), _p(x), _p(eps2), _p(noise), x.numel(), float(cfg_scale), float(sqrt_one_minus_a),
+                                       float(sqrt_a), float(sqrt_a_prev), float(dir_coef), float(sigma)), h, "crg_cfg_ddim_step")
     return _written(x)
 
 

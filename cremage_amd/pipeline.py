@@ -9,15 +9,18 @@ Step structure reproduced (file:line of the reference):
             decode_first_stage per image, clamp((x+1)/2, 0, 1)                             :1007-1015
   img2img : encode_first_stage -> get_first_stage_encoding (posterior sample * 0.18215)    :721
             t_enc = int(strength * steps); DDIM stochastic_encode + decode                 :727, :147-248
+  inpaint : modules/sd/inpaint.py:75-290 - mask + masked-image latents as c_concat (hybrid conditioning), start code from
+            np.random.RandomState(seed), DDIM eta = 1 from x_T, decode                    :160-281
 """
 from __future__ import annotations
 
 from typing import Callable, Optional
 
+import numpy as np
 import torch
 
 from . import ops
-from .ldm_hip.latent_diffusion import LatentDiffusion
+from .ldm_hip.latent_diffusion import LatentDiffusion, LatentInpaintDiffusion
 from .ldm_hip.unet import UNetModel
 from .ldm_hip.vae import AutoencoderKL
 from .samplers import DDIMSampler, EulerAncestralSampler, EulerSampler
@@ -45,6 +48,24 @@ def build_synthetic_ldm(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=to
     ldm.model.to(unet_dtype)
     ldm.first_stage_model.to(vae_dtype)
     return ldm.to(device).eval()
+
+
+def build_synthetic_inpaint_ldm(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=torch.bfloat16, vae_dtype=torch.float32,
+                                seed: int = 1234) -> LatentInpaintDiffusion:
+    """LatentInpaintDiffusion (inpainting.yaml: hybrid conditioning, 9-channel UNet) with name-keyed synthetic weights."""
+    unet = UNetModel(**dict(unet_cfg or SD15_UNET, in_channels=9))
+    vae = AutoencoderKL(vae_dd or SD15_VAE_DD, None, 4)
+    synth_fill_(unet, seed, prefix="unet.")
+    synth_fill_(vae, seed, prefix="vae.")
+    ldm = LatentInpaintDiffusion(unet, vae)
+    ldm.model.to(unet_dtype)
+    ldm.first_stage_model.to(vae_dtype)
+    return ldm.to(device).eval()
+
+
+def inpaint_start_code(seed: int, n: int, height: int, width: int) -> torch.Tensor:
+    """The inpainting start latents of a Cremage seed (inpaint.py:166-169): np.random.RandomState(seed).randn(n, 4, H/8, W/8) as fp32."""
+    return torch.from_numpy(np.random.RandomState(seed).randn(n, 4, height // 8, width // 8)).to(torch.float32)
 
 
 def build_ldm_sharded(rank: int, device, unet_cfg=None, vae_dd=None, unet_dtype=torch.bfloat16, vae_dtype=torch.float32, seed: int = 1234):
@@ -167,6 +188,38 @@ def img2img(ldm: LatentDiffusion, init_image: torch.Tensor, c: torch.Tensor, uc:
     smp.make_schedule(ddim_num_steps=steps, ddim_eta=0.0, verbose=False)
     z_enc = smp.stochastic_encode(init_latent, torch.tensor([t_enc] * b, device=init_latent.device), noise=fwd_noise)
     samples = smp.decode(z_enc, c, t_enc, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc)
+    return (decode_images(ldm, samples) if decode else None), samples
+
+
+@torch.no_grad()
+def inpaint(ldm: LatentDiffusion, image, mask, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 50, cfg_scale: float = 7.5,
+            eta: float = 1.0, seed: Optional[int] = None, noise_sampler: Optional[Callable] = None, enc_noise: Optional[torch.Tensor] = None,
+            decode: bool = True):
+    """SD1.5 inpainting as modules/sd/inpaint.py:75-290 drives it, on an inpainting LatentDiffusion (9-channel UNet, hybrid conditioning).
+
+    image [n, 3, H, W] in [-1, 1] and mask [n, 1, H, W] (white = repaint; thresholded at 0.5) on the model's device, H and W multiples of
+    64 (postprocess.inpaint_batch builds both from PIL images as make_batch_sd does, postprocess.resize_with_padding pads to 64).
+    c_concat = cat([mask nearest-downsampled to H/8 x W/8, get_first_stage_encoding(encode(image * (mask < 0.5)))]) (:218-227) - one
+    tensor in both the conditional and the unconditional dict (:244-245), so the HIP UNet may share its CFG prefix; start code from
+    np.random.RandomState(seed) (:166-169; torch.randn when seed is None); DDIM with eta (1.0 in the reference) from that start code;
+    decode and clamp((x + 1) / 2, 0, 1).  `enc_noise`: the posterior sample's noise; `noise_sampler(sigma, index)`: DDIM's per-step z.
+    Returns (images [n, 3, H, W] in [0, 1] or None, final latents)."""
+    import torch.nn.functional as F
+    n = image.shape[0]
+    dev = ldm.device
+    image = image.to(dev, torch.float32)
+    m = (mask.to(dev, torch.float32) >= 0.5).to(torch.float32)
+    masked = image * (m < 0.5)
+    z_masked = ldm.get_first_stage_encoding(ldm.encode_first_stage(masked), enc_noise).to(torch.float32)
+    hl, wl = z_masked.shape[-2:]  # H/8 x W/8 with the SD VAE
+    m_lat = F.interpolate(m, size=(hl, wl))  # nearest, the reference's default mode
+    c_cat = torch.cat([m_lat, z_masked], dim=1)
+    cond = {"c_concat": [c_cat], "c_crossattn": [c]}
+    uc_full = {"c_concat": [c_cat], "c_crossattn": [uc]} if uc is not None else None
+    x_T = inpaint_start_code(seed, n, 8 * hl, 8 * wl).to(dev) if seed is not None else torch.randn((n, 4, hl, wl), device=dev)
+    smp = DDIMSampler(ldm)
+    samples, _ = smp.sample(steps, n, [4, hl, wl], cond, eta=eta, x_T=x_T, unconditional_guidance_scale=cfg_scale,
+                            unconditional_conditioning=uc_full, noise_sampler=noise_sampler)
     return (decode_images(ldm, samples) if decode else None), samples
 
 

@@ -15,6 +15,10 @@ that a Cremage user finds the whole second-pass chain:
   hires-fix pixel upscaler         image_generator.py:1020-1026 -> cremage/utils/ml_utils.py:28-71: cv2.resize(INTER_LANCZOS4) on uint8.
                                    cv2's 8x8 Lanczos-4 kernel is not PIL's Lanczos-3: `upscale_uint8` does the same uint8 round trip
                                    with PIL's filter and is labelled an approximation (unpinned).
+  inpainting                       modules/sd/inpaint.py: padding to multiples of 64 (image_utils.py:228-300, white, aspect kept),
+                                   the luminance mask / masked image of make_batch_sd (:45-72), and the default compositing
+                                   (:357-398, use_seamless_clone = False): 11x11 Gaussian blur of the mask, alpha blend over the
+                                   original, crop of the padding.  The blur is restated in numpy (see `gaussian_blur_11`).
 
 Pure Python + PIL + numpy; nothing here touches the HIP library.
 """
@@ -144,6 +148,76 @@ def upscale_uint8(samples: torch.Tensor, width: int, height: int) -> torch.Tenso
     for i in range(u8.shape[0]):
         out[i] = np.asarray(Image.fromarray(u8[i]).resize((width, height), resample=Image.LANCZOS), dtype=np.float32)
     return (torch.from_numpy(out).permute(0, 3, 1, 2) / 255.0).float().to(samples.device)
+
+
+# ---------------------------------------------------------------------------------------------- inpainting
+def bbox_for_multiple_of_64(width: int, height: int) -> Tuple[int, int]:
+    """(width, height) rounded UP to multiples of 64 (image_utils.py:228-235)."""
+    up = lambda e: -(-int(e) // 64) * 64
+    return up(width), up(height)
+
+
+def resize_with_padding(image, target_width: int, target_height: int, color: str = "#ffffff"):
+    """image_utils.py:251-310 with return_bbox=True -> (RGBA image of the target size, (x1, y1, x2, y2) of the unpadded area): the image
+    resized (Lanczos, aspect kept) to fill the target's width - or its height when the resized height would not fit - and centred on a
+    `color` canvas; an odd padding puts the extra pixel before the image.  As in the reference, an image that is already
+    target_width x target_width comes back unchanged (the reference compares the height with the target WIDTH there)."""
+    from PIL import Image
+    w, h = image.size
+    if w == target_width and h == target_width:
+        return image, (0, 0, w, h)
+    base = Image.new("RGBA", (target_width, target_height), color)
+    new_h = int(h * (target_width / w))
+    if new_h > target_height:  # fit the height instead
+        new_w, new_h = int(w * (target_height / h)), target_height
+        pad_w = target_width - new_w
+        px, py = int(pad_w / 2) + pad_w % 2, 0
+    else:
+        new_w = target_width
+        pad_h = target_height - new_h
+        px, py = 0, int(pad_h / 2) + pad_h % 2
+    base.paste(image.resize((int(new_w), int(new_h)), resample=Image.LANCZOS), (px, py))
+    return base, (px, py, px + new_w, py + new_h)
+
+
+def inpaint_batch(image, mask):
+    """make_batch_sd (inpaint.py:45-72) for one image: PIL image + PIL mask (white = repaint) -> (image [1, 3, H, W] in [-1, 1],
+    mask [1, 1, H, W] in {0, 1} from the luminance ("L") thresholded at 0.5, masked_image = image * (mask < 0.5)) as fp32 CPU tensors."""
+    img = torch.from_numpy(np.array(image.convert("RGB"))[None].transpose(0, 3, 1, 2).copy()).to(torch.float32) / 127.5 - 1.0
+    m = np.array(mask.convert("L")).astype(np.float32) / 255.0
+    m = torch.from_numpy((m >= 0.5).astype(np.float32)[None, None])
+    return img, m, img * (m < 0.5)
+
+
+def gaussian_blur_11(a: np.ndarray) -> np.ndarray:
+    """cv.GaussianBlur(a, (11, 11), 0) of a uint8 [H, W] image: sigma = 0.3 * ((11 - 1) * 0.5 - 1) + 0.8 = 2.0 (cv2's rule for sigma 0),
+    separable normalised kernel, BORDER_REFLECT_101 (numpy's "reflect"), rounded to uint8.  cv2 filters uint8 images in fixed point
+    (16-bit kernel taps), so its result can differ from this float64 restatement by 1 LSB on some pixels."""
+    k = np.exp(-((np.arange(11) - 5.0) ** 2) / (2.0 * 2.0 ** 2))
+    k /= k.sum()
+    p = np.pad(a.astype(np.float64), 5, mode="reflect")
+    rows = sum(k[i] * p[:, i:i + a.shape[1]] for i in range(11))
+    out = sum(k[i] * rows[i:i + a.shape[0], :] for i in range(11))
+    return np.clip(np.floor(out + 0.5), 0, 255).astype(np.uint8)
+
+
+def _cv_gray(rgb: np.ndarray) -> np.ndarray:
+    """cv.cvtColor(..., COLOR_RGB2GRAY) on uint8: 0.299 R + 0.587 G + 0.114 B in cv2's 14-bit fixed point."""
+    r, g, b = (rgb[..., i].astype(np.int64) for i in range(3))
+    return ((r * 4899 + g * 9617 + b * 1868 + (1 << 13)) >> 14).astype(np.uint8)
+
+
+def composite_inpaint(original, inpainted, mask, bbox: Optional[Tuple[int, int, int, int]] = None):
+    """The reference's default compositing (inpaint.py:357-398, use_seamless_clone = False): the mask's grey level blurred with an
+    11x11 Gaussian is the weight of the inpainted image over the original (float32 blend, truncated to uint8); `bbox` (the padding's
+    inner box from resize_with_padding) is cropped out at the end.  PIL images in, PIL RGB image out."""
+    from PIL import Image
+    orig = np.asarray(original.convert("RGB")).astype(np.float32)
+    inp = np.asarray(inpainted.convert("RGB")).astype(np.float32)
+    m = gaussian_blur_11(_cv_gray(np.asarray(mask.convert("RGB")))).astype(np.float32) / np.float32(255.0)
+    out = inp * m[..., None] + orig * (np.float32(1.0) - m)[..., None]
+    img = Image.fromarray(np.clip(out, 0, 255).astype(np.uint8))
+    return img.crop(bbox) if bbox is not None else img
 
 
 # ---------------------------------------------------------------------------------------------- PNG + generation_data

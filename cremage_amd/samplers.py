@@ -153,13 +153,7 @@ class LDMWrapperForKDiffusion(nn.Module):
         if self._c_in is None:
             c, uc = self.c, self.unconditional_conditioning
             if isinstance(c, dict):
-                assert isinstance(uc, dict)
-                c_in = dict()
-                for k in c:
-                    if isinstance(c[k], list):
-                        c_in[k] = [torch.cat([uc[k][i], c[k][i]]) for i in range(len(c[k]))]
-                    else:
-                        c_in[k] = torch.cat([uc[k], c[k]])
+                c_in = cat_cond_dict(c, uc)
             else:
                 c_in = {"c_crossattn": [torch.cat([uc, c])]}
                 LDMWrapperForKDiffusion._cat_memo = (c, uc, c_in, (c._version, uc._version))
@@ -214,6 +208,25 @@ class LDMWrapperForKDiffusion(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.apply_model(*args, **kwargs)
+
+
+def cat_cond_dict(c: dict, uc: dict) -> dict:
+    """The batch-doubled dict conditioning of a CFG call (ddim.py:553-562, ldm_wrapper_for_k_diffusion.py:67-92): cat([uc[k], c[k]]) per
+    entry.  A `c_concat` entry whose two halves are ONE tensor object (inpaint.py:244-245 puts the same c_cat in both dicts) is marked
+    as batch-doubled (ops.mark_cfg_dup), so that the HIP UNet may share its CFG prefix; equal values in two objects are not marked - the
+    mark is a promise of the caller, never inferred from data."""
+    assert isinstance(uc, dict)
+    c_in = dict()
+    for k in c:
+        if isinstance(c[k], list):
+            c_in[k] = [torch.cat([uc[k][i], c[k][i]]) for i in range(len(c[k]))]
+            if k == "c_concat":
+                for i, t in enumerate(c_in[k]):
+                    if uc[k][i] is c[k][i]:
+                        _mark_dup(t)
+        else:
+            c_in[k] = torch.cat([uc[k], c[k]])
+    return c_in
 
 
 def _mark_dup(x_in):
@@ -436,8 +449,8 @@ def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timestep
 
 
 class DDIMSampler(object):
-    """ddim.py (eta = 0 as the img2img driver uses it): make_schedule :38-75, stochastic_encode :615-654,
-    decode :657-676, p_sample_ddim :530-612."""
+    """ddim.py: make_schedule :38-75, sample / ddim_sampling :78-190 (from x_T, any eta: the inpainting driver runs eta = 1),
+    stochastic_encode :615-654, decode :657-676 (eta = 0, the img2img driver), p_sample_ddim :530-612."""
 
     def __init__(self, model, schedule="linear", **kwargs):
         self.model = model
@@ -445,15 +458,28 @@ class DDIMSampler(object):
         self.schedule = schedule
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=False):
-        assert ddim_eta == 0., "only the deterministic (eta = 0) DDIM of the img2img driver is restated"
         self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps)
         acp = self.model.alphas_cumprod.detach().float().cpu()
         assert acp.shape[0] == self.ddpm_num_timesteps
         dev = self.model.device
-        self.ddim_alphas = acp[self.ddim_timesteps].to(dev)
-        self.ddim_alphas_prev = torch.cat([acp[:1], acp[self.ddim_timesteps[:-1]]]).to(dev)
+        a = acp[self.ddim_timesteps]
+        a_prev = torch.cat([acp[:1], acp[self.ddim_timesteps[:-1]]])
+        self.ddim_alphas = a.to(dev)
+        self.ddim_alphas_prev = a_prev.to(dev)
         self.ddim_sqrt_one_minus_alphas = (1. - self.ddim_alphas).sqrt()
-        self.ddim_sigmas = torch.zeros_like(self.ddim_alphas)
+        if ddim_eta == 0.:
+            sig = torch.zeros_like(a)
+        else:
+            # make_ddim_sampling_parameters (util.py:63-74): eta * sqrt((1 - a_prev) / (1 - a) * (1 - a / a_prev)) in fp64 on the fp32
+            # table values, where the reference's `1 - a` is a torch fp32 subtraction; p_sample_ddim then broadcasts it as fp32
+            sig = (ddim_eta * torch.sqrt((1. - a_prev.double()) / (1. - a).double() * (1. - a.double() / a_prev.double()))).float()
+        self.ddim_sigmas = sig.to(dev)
+        # the fp32 scalars p_sample_ddim computes from the tables per step (ddim.py:581-604), for the fused step: torch.full((b,1,1,1),
+        # table[index]) -> fp32, then .sqrt(), 1 - a_prev - sigma ** 2 as fp32 tensor arithmetic
+        sq1ma = (1. - a).sqrt()
+        dir_coef = (1. - a_prev - sig ** 2).sqrt()
+        self._step_scalars = [(float(sq1ma[i]), float(a[i].sqrt()), float(a_prev[i].sqrt()), float(dir_coef[i]), float(sig[i]))
+                              for i in range(a.shape[0])]
 
     @torch.no_grad()
     def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):
@@ -464,7 +490,8 @@ class DDIMSampler(object):
         return ex(self.ddim_alphas.sqrt()) * x0 + ex(self.ddim_sqrt_one_minus_alphas) * noise
 
     @torch.no_grad()
-    def p_sample_ddim(self, x, c, t, index, unconditional_guidance_scale=1., unconditional_conditioning=None):
+    def p_sample_ddim(self, x, c, t, index, unconditional_guidance_scale=1., unconditional_conditioning=None, noise=None):
+        """One step of the elementwise chain; `noise` (z of noise_like) is added as sigma_t * z when this step's sigma is not 0."""
         if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
             e_t = self.model.apply_model(x, t, c)
         else:
@@ -475,8 +502,92 @@ class DDIMSampler(object):
             e_t = e_t_uncond + unconditional_guidance_scale * (e_t - e_t_uncond)
         a_t, a_prev = self.ddim_alphas[index], self.ddim_alphas_prev[index]
         pred_x0 = (x - self.ddim_sqrt_one_minus_alphas[index] * e_t) / a_t.sqrt()
-        dir_xt = (1. - a_prev).sqrt() * e_t
-        return a_prev.sqrt() * pred_x0 + dir_xt, pred_x0
+        sigma = self._step_scalars[index][4] if hasattr(self, "_step_scalars") else 0.
+        if sigma == 0.:
+            dir_xt = (1. - a_prev).sqrt() * e_t
+            return a_prev.sqrt() * pred_x0 + dir_xt, pred_x0
+        sigma_t = self.ddim_sigmas[index]
+        dir_xt = (1. - a_prev - sigma_t ** 2).sqrt() * e_t
+        return a_prev.sqrt() * pred_x0 + dir_xt + sigma_t * noise, pred_x0
+
+    _cat_memo = None  # (leaves, versions, c_in): one doubled conditioning per (c, uc) across sampler runs, so that the modules' K/V cache
+    #                   and a captured hipGraph (keyed on the conditioning's identity) survive from batch to batch
+
+    @staticmethod
+    def _leaves(cond):
+        if isinstance(cond, dict):
+            return tuple((k, i, t) for k in sorted(cond) for i, t in enumerate(cond[k] if isinstance(cond[k], list) else [cond[k]]))
+        return (("", 0, cond),)
+
+    def _cat_cond(self, c, uc):
+        leaves = self._leaves(uc) + self._leaves(c)
+        m = DDIMSampler._cat_memo
+        if m is not None and len(m[0]) == len(leaves) and all(a[:2] == b[:2] and a[2] is b[2] for a, b in zip(m[0], leaves)) \
+                and m[1] == tuple(t._version for _, _, t in leaves):
+            return m[2]
+        c_in = cat_cond_dict(c, uc) if isinstance(c, dict) else torch.cat([uc, c])
+        DDIMSampler._cat_memo = (leaves, tuple(t._version for _, _, t in leaves), c_in)
+        return c_in
+
+    def _time_rows(self, t_rep):
+        """The HIP UNet's hoisted timestep work for the table of doubled timesteps `t_rep` [S, 2b] (UNetModel.time_rows), attached
+        to the per-step rows; plain rows when the network does not offer it."""
+        from . import ops
+        rows = [t_rep[i] for i in range(t_rep.shape[0])]
+        dm = getattr(getattr(self.model, "model", None), "diffusion_model", None)
+        f = getattr(dm, "time_rows", None)
+        if f is not None and t_rep.is_cuda and ops.TIME_ROWS:
+            tr = f(t_rep)
+            for i, r in enumerate(rows):
+                ops.attach_time_rows(r, tr[i], dm)
+        return rows
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0., x_T=None, verbose=False,
+               unconditional_guidance_scale=1., unconditional_conditioning=None, noise_sampler=None, **kwargs):
+        """ddim.py:78-190 (DDIM from x_T over the whole uniform schedule) -> (samples, None).  `conditioning` / `unconditional_conditioning`
+        are tensors or dicts ({"c_concat": [...], "c_crossattn": [...]} for the inpainting model).  `noise_sampler(sigma, index)` returns
+        the step's z (noise_like, ddim.py:603) - e.g. pipeline.trajectory_noise_sampler; by default torch.randn is drawn on the steps
+        whose sigma is not 0.  With CFG on fp32 device latents and no callback, guidance + the DDIM update + the noise term run as ONE
+        kernel per step (crg_cfg_ddim_step) and the UNet's timestep work is computed once for the schedule; otherwise the elementwise
+        chain of p_sample_ddim runs."""
+        if kwargs.get("mask") is not None or kwargs.get("x0") is not None:
+            raise NotImplementedError("DDIMSampler.sample: mask / x0 blending is not restated")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        C, H, W = shape
+        size = (batch_size, C, H, W)
+        dev = self.model.device
+        x = torch.randn(size, device=dev) if x_T is None else x_T
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        guided = uc is not None and scale != 1.
+        self._c_in = self._cat_cond(conditioning, uc) if guided else None
+        time_range = np.flip(self.ddim_timesteps)
+        total = self.ddim_timesteps.shape[0]
+        fused = guided and callback is None and x.is_cuda and x.dtype == torch.float32
+        if fused:
+            from . import ops
+            x = x.clone().contiguous()  # updated in place by the fused step
+            t_rep = torch.tensor(time_range.copy(), dtype=torch.long).reshape(-1, 1).expand(-1, 2 * batch_size).contiguous().to(x.device)
+            t_rows = self._time_rows(t_rep)
+        for i, step in enumerate(time_range):
+            index = total - i - 1
+            sigma = self._step_scalars[index][4]
+            z = None
+            if sigma != 0.:
+                z = noise_sampler(sigma, index) if noise_sampler is not None else torch.randn(size, device=x.device)
+            if fused:
+                xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                xx.copy_(x.unsqueeze(0).expand_as(xx))  # cat([x] * 2) as one copy
+                e2 = self.model.apply_model(_mark_dup(xx.view((2 * batch_size,) + tuple(x.shape[1:]))), t_rows[i], self._c_in)
+                ops.cfg_ddim_step_(x, e2.contiguous(), z.contiguous() if z is not None else None, scale, *self._step_scalars[index])
+                continue
+            ts = torch.full((batch_size,), int(step), device=x.device, dtype=torch.long)
+            x, _ = self.p_sample_ddim(x, conditioning, ts, index=index, unconditional_guidance_scale=scale,
+                                      unconditional_conditioning=uc, noise=z)
+            if callback:
+                callback(i)
+        self._c_in = None
+        return x, None
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,

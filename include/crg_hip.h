@@ -311,7 +311,8 @@ int crg_softmax_rows(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t
 /* ---- small-channel direct conv ----------------------------------------------------------------
  * conv_in (4->320, openaimodel.py:551; VAE 4->512 model.py:494; encoder 3->128 :390), conv_out
  * (320->4, :755; VAE 128->3 :536; encoder 512->8 :435) and the 1x1 quant_conv / post_quant_conv
- * (autoencoder.py:302-303): Cin <= 8 or Cout <= 8, ksize 3 (pad 1) or 1, stride 1.
+ * (autoencoder.py:302-303): Cin <= 8 or Cout <= 8, ksize 3 (pad 1) or 1, stride 1.  Cin = 9 (the inpainting UNet's conv_in: 4 latent +
+ * 1 mask + 4 masked-image channels, inpainting.yaml) takes the thin-input path too, with Cout a multiple of 8.
  * x: [N][H][W][Cin] x_dtype, w: fp32 [Cout][Cin][k][k] (checkpoint layout), bias fp32, y y_dtype. */
 int crg_conv_small(crg_ctx* ctx, void* stream, const void* x, const float* w, const float* bias, void* y,
                    int N, int H, int W, int Cin, int Cout, int ksize, int x_dtype, int y_dtype);
@@ -326,6 +327,11 @@ int crg_nchw_to_nhwc(crg_ctx* ctx, void* stream, const void* src, void* dst, int
                      int dst_dtype);
 int crg_nhwc_to_nchw(crg_ctx* ctx, void* stream, const void* src, void* dst, int N, int C, int HW, int src_dtype,
                      int dst_dtype);
+/* cat([a, b], dim 1) of two NCHW tensors of src_dtype -> one NHWC tensor of dst_dtype with Ca + Cb channels, the concat folded into the
+ * transpose (the hybrid conditioning's torch.cat([x] + c_concat, dim=1), ddpm.py:1520-1523, at the UNet boundary).
+ * a: [N][Ca][HW], b: [N][Cb][HW], dst: [N][HW][Ca + Cb]. */
+int crg_nchw2_to_nhwc(crg_ctx* ctx, void* stream, const void* src_a, const void* src_b, void* dst, int N, int Ca, int Cb, int HW,
+                      int src_dtype, int dst_dtype);
 /* y = a*x + b elementwise with dtype conversion (latent scaling z/0.18215, clamp((x+1)/2,0,1)) */
 int crg_affine_cast(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, float lo,
                     float hi, int src_dtype, int dst_dtype);
@@ -339,6 +345,16 @@ int crg_affine_cast(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t 
  * eps: [2][n] fp32 (unconditional half first - the batch-doubled UNet output), x / noise: [n] fp32. */
 int crg_cfg_euler_step(crg_ctx* ctx, void* stream, void* x, const void* eps, const void* noise, int64_t n, float sigma,
                        float dt, float cfg_scale, float noise_scale);
+
+/* One DDIM step with classifier-free guidance, in place on x (ddim.py:540-612 p_sample_ddim, one fp32 rounding per operation):
+ *   e  = eu + cfg_scale * (ec - eu)                                   guidance
+ *   x0 = (x - sqrt_one_minus_a * e) / sqrt_a                          pred_x0
+ *   x  = sqrt_a_prev * x0 + dir_coef * e [+ sigma * noise]            dir_xt, noise_like
+ * with the per-step scalars rounded to fp32 by the caller: sqrt_one_minus_a = sqrt(1 - a_t), sqrt_a = sqrt(a_t),
+ * sqrt_a_prev = sqrt(a_prev), dir_coef = sqrt(1 - a_prev - sigma^2).  sigma == 0 reads no noise (noise may be NULL).
+ * eps: [2][n] fp32 (unconditional half first), x / noise: [n] fp32. */
+int crg_cfg_ddim_step(crg_ctx* ctx, void* stream, void* x, const void* eps, const void* noise, int64_t n, float cfg_scale,
+                      float sqrt_one_minus_a, float sqrt_a, float sqrt_a_prev, float dir_coef, float sigma);
 
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
