@@ -591,6 +591,44 @@ extern "C" int crg_cfg_ddim_step(crg_ctx* ctx, void* stream, void* x, const void
   return 0;
 }
 
+namespace {
+// One fused DPM++ 2M step (see include/crg_hip.h): DiscreteDenoiser (EpsScaling, c_skip = 1) on both CFG halves, VanillaCFG and
+// DPMPP2MSampler.sampler_step's update, one fp32 rounding per operation in the reference's order (no FMA contraction).  `old` is
+// read only on an advanced step, so the first step may pass an uninitialised buffer; it always receives this step's denoised value.
+__global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(float* __restrict__ x, const float* __restrict__ eps,
+                                                               float* __restrict__ old, long n, float c_out, float cfg, float m1,
+                                                               float m2, float m3, float m4, int advanced) {
+#pragma clang fp contract(off)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float xv = x[i];
+    const float den_u = eps[i] * c_out + xv;
+    const float den_c = eps[n + i] * c_out + xv;
+    const float den = den_u + cfg * (den_c - den_u);
+    float xn;
+    if (advanced) {
+      const float dd = m3 * den - m4 * old[i];
+      xn = m1 * xv - m2 * dd;
+    } else {
+      xn = m1 * xv - m2 * den;
+    }
+    x[i] = xn;
+    old[i] = den;
+  }
+}
+}  // namespace
+
+extern "C" int crg_cfg_dpmpp2m_step(crg_ctx* ctx, void* stream, void* x, const void* eps, void* old_den, int64_t n, float c_out,
+                                    float cfg_scale, float m1, float m2, float m3, float m4, int advanced) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, n > 0 && x && eps && old_den, "cfg_dpmpp2m_step: empty input");
+  hipStream_t st = (hipStream_t)stream;
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, (advanced ? 11.0 : 8.0) * n, 4.0 * n * (advanced ? 6 : 5));
+  hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel, dim3(grid_for(n)), dim3(256), 0, st, (float*)x, (const float*)eps, (float*)old_den,
+                     (long)n, c_out, cfg_scale, m1, m2, m3, m4, advanced ? 1 : 0);
+  CRG_CHECK_LAUNCH(ctx, "cfg_dpmpp2m_step");
+  return 0;
+}
+
 extern "C" int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, n > 0, "axpby: empty");

@@ -1088,6 +1088,22 @@ def cfg_ddim_step_(x: torch.Tensor, eps2: torch.Tensor, noise: Optional[torch.Te
     return _written(x)
 
 
+def cfg_dpmpp2m_step_(x: torch.Tensor, eps2: torch.Tensor, old_den: torch.Tensor, c_out: float, cfg_scale: float, m1: float, m2: float,
+                      m3: float, m4: float, advanced: bool) -> torch.Tensor:
+    """In-place fused SDXL DPM++ 2M step (crg_cfg_dpmpp2m_step): x fp32 [b, ...], eps2 fp32 [2b, ...] (the raw network output,
+    uncond half first), old_den fp32 [b, ...] (the previous step's denoised value, read only when `advanced`; overwritten with this
+    step's).  c_out = -sigma (quantised); m1..m4 the fp32 multipliers of DPMPP2MSampler.get_mult (see include/crg_hip.h)."""
+    _need_cuda(x, eps2, old_den)
+    if x.dtype != torch.float32 or eps2.dtype != torch.float32 or old_den.dtype != torch.float32 or not x.is_contiguous() \
+            or not eps2.is_contiguous() or not old_den.is_contiguous() or eps2.numel() != 2 * x.numel() or old_den.numel() != x.numel():
+        raise L.CrgError("cfg_dpmpp2m_step_: contiguous fp32 x [b,...], eps [2b,...] and old_den [b,...] expected")
+    h = _h(x)
+    L.check(L.load().crg_cfg_dpmpp2m_step(h, _st(), _p(x), _p(eps2), _p(old_den), x.numel(), float(c_out), float(cfg_scale), float(m1),
+                                          float(m2), float(m3), float(m4), 1 if advanced else 0), h, "crg_cfg_dpmpp2m_step")
+    _written(old_den)
+    return _written(x)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

@@ -229,6 +229,10 @@ SDXL_UNET = dict(adm_in_channels=2816, num_classes="sequential", use_checkpoint=
                  use_linear_in_transformer=True, transformer_depth=[1, 2, 10], context_dim=2048,
                  spatial_transformer_attn_type="softmax-xformers")  # sd_xl_base.yaml:17-33
 SDXL_VAE_DD = dict(SD15_VAE_DD, attn_type="vanilla-xformers")       # sd_xl_base.yaml:80-92
+SDXL_REFINER_UNET = dict(adm_in_channels=2560, num_classes="sequential", use_checkpoint=True, in_channels=4, out_channels=4,
+                         model_channels=384, attention_resolutions=[4, 2], num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_head_channels=64,
+                         use_linear_in_transformer=True, transformer_depth=4, context_dim=[1280, 1280, 1280, 1280],
+                         spatial_transformer_attn_type="softmax-xformers")  # sd_xl_refiner.yaml:17-33
 
 
 def build_synthetic_sdxl(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=torch.bfloat16, vae_dtype=torch.float32, seed: int = 1234,
@@ -248,16 +252,37 @@ def build_synthetic_sdxl(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=t
     return eng.to(device).eval()
 
 
+def build_synthetic_sdxl_refiner(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=torch.bfloat16, vae_dtype=torch.float32,
+                                 seed: int = 1234, fill: bool = True, first_stage=None):
+    """The refiner's DiffusionEngine (sd_xl_refiner.yaml: 2.26 B-parameter UNet, the same first stage and denoiser as the base) with
+    name-keyed synthetic weights.  `first_stage`: an existing first-stage model to share (the base engine's), instead of a new one."""
+    from .sgm_hip.sampling import DiffusionEngine
+    from .sgm_hip.unet import UNetModel as SgmUNet
+    unet = SgmUNet(**(unet_cfg or SDXL_REFINER_UNET))
+    if fill:
+        synth_fill_(unet, seed, prefix="sgm_unet.")
+    vae = first_stage
+    if vae is None:
+        vae = AutoencoderKL(vae_dd or SDXL_VAE_DD, None, 4)
+        if fill:
+            synth_fill_(vae, seed, prefix="vae.")
+        vae.to(vae_dtype)
+    eng = DiffusionEngine(unet, vae, 0.13025)
+    eng.model.to(unet_dtype)
+    return eng.to(device).eval()
+
+
 @torch.no_grad()
 def txt2img_sdxl(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
-                 x0: Optional[torch.Tensor] = None, decode: bool = True):
+                 x0: Optional[torch.Tensor] = None, decode: bool = True, sampler: str = "euler_edm", stage2strength: Optional[float] = None):
     """run_txt2img -> do_sample (modules/sdxl/sdxl_pipeline/sdxl_image_generator_utils.py:559-772): randn [b,4,H/8,W/8]
     (:695), sampler(denoiser, randn, cond=c, uc=uc) (:707), decode_first_stage in fp32 (:727-734), clamp((x+1)/2, 0, 1).
-    c / uc: {"crossattn": [b,77,2048], "vector": [b,2816]}."""
+    c / uc: {"crossattn": [b,77,2048], "vector": [b,2816]}.  `sampler`: "euler_edm" or "dpmpp2m"; `stage2strength`: the refiner
+    strength of a two-stage run, whose base stage stops early (Txt2NoisyDiscretizationWrapper)."""
     b = c["crossattn"].shape[0]
     if x0 is None:
         x0 = torch.randn((b, 4, height // 8, width // 8), device=c["crossattn"].device)
-    samples = eng.sample(x0, c, uc, steps, cfg_scale)
+    samples = eng.sample(x0, c, uc, steps, cfg_scale, sampler=sampler, stage2strength=stage2strength)
     if not decode:
         return None, samples
     x = eng.decode_first_stage(samples)
@@ -266,14 +291,49 @@ def txt2img_sdxl(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 
 
 @torch.no_grad()
 def img2img_sdxl(eng, init_image: torch.Tensor, c: dict, uc: dict, *, steps: int = 30, strength: float = 0.3, cfg_scale: float = 5.0,
-                 enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, decode: bool = True):
+                 enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, decode: bool = True,
+                 sampler: str = "euler_edm", stage2strength: Optional[float] = None):
     """run_img2img -> do_img2img (sdxl_image_generator_utils.py:775-1025); with strength 0.3 on a face crop this is the second
-    pass of the auto-face-fix (modules/sdxl/face_img2img... -> the same do_img2img).  init_image [b,3,H,W] in [-1,1]."""
-    samples = eng.img2img(init_image, c, uc, steps, strength, cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise)
+    pass of the auto-face-fix (modules/sdxl/face_img2img... -> the same do_img2img).  init_image [b,3,H,W] in [-1,1].
+    `sampler` / `stage2strength` as in txt2img_sdxl."""
+    samples = eng.img2img(init_image, c, uc, steps, strength, cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise, sampler=sampler,
+                          stage2strength=stage2strength)
     if not decode:
         return None, samples
     x = eng.decode_first_stage(samples)
     return ops.affine_cast(x, 0.5, 0.5, torch.float32, 0.0, 1.0), samples
+
+
+@torch.no_grad()
+def refine_sdxl(refiner, z: torch.Tensor, c2: dict, uc2: dict, *, steps: int, strength: float, cfg_scale: float, sampler: str = "dpmpp2m",
+                decode: bool = True):
+    """The refiner stage on base latents z [b,4,H/8,W/8] (apply_refiner, sdxl_image_generator.py:307-347): Img2Img-pruned schedule
+    of `steps` at `strength`, no added noise, then decode and clamp((x+1)/2, 0, 1).  c2 / uc2: the refiner conditioner's output,
+    {"crossattn": [b,77,1280], "vector": [b,2560]}.  Returns (images or None, latents)."""
+    samples = refiner.refine(z, c2, uc2, steps, strength, cfg_scale, sampler=sampler)
+    if not decode:
+        return None, samples
+    x = refiner.decode_first_stage(samples)
+    return ops.affine_cast(x, 0.5, 0.5, torch.float32, 0.0, 1.0), samples
+
+
+@torch.no_grad()
+def txt2img_sdxl_refined(base, refiner, c: dict, uc: dict, c2: dict, uc2: dict, *, steps: int = 30, refiner_strength: float = 0.15,
+                         cfg_scale: float = 5.0, sampler: str = "dpmpp2m", height: int = 1024, width: int = 1024,
+                         x0: Optional[torch.Tensor] = None, decode: bool = True):
+    """SDXL txt2img with the refiner stage (sdxl_use_refiner, sdxl_image_generator.py:420-424, :555-635): the base samples with the
+    schedule's last sigmas dropped (Txt2Noisy, stage2strength = refiner_strength) and is not decoded; the refiner continues from its
+    latents (refine_sdxl) and its first stage decodes.  refiner_strength == 0 turns the refiner off, as the reference does: the
+    result is txt2img_sdxl's.  Returns (images or None, base latents, final latents)."""
+    if refiner_strength == 0:
+        images, samples = txt2img_sdxl(base, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, decode=decode,
+                                       sampler=sampler)
+        return images, samples, samples
+    _, z = txt2img_sdxl(base, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, decode=False, sampler=sampler,
+                        stage2strength=refiner_strength)
+    images, samples = refine_sdxl(refiner, z, c2, uc2, steps=steps, strength=refiner_strength, cfg_scale=cfg_scale, sampler=sampler,
+                                  decode=decode)
+    return images, z, samples
 
 
 @torch.no_grad()

@@ -356,6 +356,18 @@ int crg_cfg_euler_step(crg_ctx* ctx, void* stream, void* x, const void* eps, con
 int crg_cfg_ddim_step(crg_ctx* ctx, void* stream, void* x, const void* eps, const void* noise, int64_t n, float cfg_scale,
                       float sqrt_one_minus_a, float sqrt_a, float sqrt_a_prev, float dir_coef, float sigma);
 
+/* One SDXL DPM++ 2M step with classifier-free guidance, in place on x (sgm DiscreteDenoiser with EpsScaling, VanillaCFG and
+ * DPMPP2MSampler.sampler_step, sampling.py:459-549; one fp32 rounding per operation, in the reference's order):
+ *   den_u = eu * c_out + x,  den_c = ec * c_out + x                    c_skip = 1, c_out = -sigma (quantised)
+ *   den   = den_u + cfg_scale * (den_c - den_u)                        guidance
+ *   x     = m1 * x - m2 * den                                          advanced == 0 (first step, next sigma == 0)
+ *   x     = m1 * x - m2 * (m3 * den - m4 * old_den)                    advanced != 0
+ *   old_den = den
+ * m1..m4 are the fp32 values of get_mult (sampling_utils.py / sampling.py:459-486) for the step.  old_den is read only when
+ * advanced != 0 and always overwritten.  eps: [2][n] fp32 (unconditional half first), x / old_den: [n] fp32. */
+int crg_cfg_dpmpp2m_step(crg_ctx* ctx, void* stream, void* x, const void* eps, void* old_den, int64_t n, float c_out, float cfg_scale,
+                         float m1, float m2, float m3, float m4, int advanced);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
