@@ -82,6 +82,19 @@ class ConvArgs(C.Structure):
     ]
 
 
+STEP_EULER_A, STEP_HEUN_1, STEP_HEUN_2, STEP_DPMPP2S_1, STEP_DPMPP2S_2, STEP_LMS = range(6)  # CRG_STEP_*
+
+
+class SamplerStepArgs(C.Structure):
+    _fields_ = [
+        ("kind", c_int), ("n", c_int64),
+        ("x", c_void_p), ("eps", c_void_p), ("x2", c_void_p), ("d", c_void_p), ("hist", c_void_p * 3), ("noise", c_void_p),
+        ("c_out", c_float), ("cfg_scale", c_float), ("sigma", c_float), ("dt", c_float), ("sigma_up", c_float), ("s_noise", c_float),
+        ("m", c_float * 4), ("coef", c_float * 4),
+        ("n_hist", c_int), ("one_call", c_int), ("add_noise", c_int),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -135,6 +148,7 @@ SIGNATURES = {
                                   c_float]),
     "crg_cfg_dpmpp2m_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                      c_float, c_int]),
+    "crg_cfg_sampler_step": (c_int, [c_void_p, c_void_p, C.POINTER(SamplerStepArgs)]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

@@ -629,6 +629,112 @@ extern "C" int crg_cfg_dpmpp2m_step(crg_ctx* ctx, void* stream, void* x, const v
   return 0;
 }
 
+namespace {
+// One fused k-sampler evaluation step (see include/crg_hip.h, crg_sampler_step_args): the denoiser scalings and the guidance of the
+// evaluation's input xin, then the kind's update, one fp32 rounding per operation in the reference's order (no FMA contraction).
+// The arguments travel by value (kernel arguments); a buffer the kind does not use on this step is never dereferenced.
+__global__ __launch_bounds__(256) void cfg_sampler_step_kernel(crg_sampler_step_args a) {
+#pragma clang fp contract(off)
+  const long n = (long)a.n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const bool second = a.kind == CRG_STEP_HEUN_2 || a.kind == CRG_STEP_DPMPP2S_2;
+    const float xv = a.x[i];
+    const float xin = second ? a.x2[i] : xv;
+    const float den_u = a.eps[i] * a.c_out + xin;
+    const float den_c = a.eps[n + i] * a.c_out + xin;
+    const float den = den_u + a.cfg_scale * (den_c - den_u);
+    float xn = xv;
+    bool noised = false, store_x = true;
+    switch (a.kind) {
+      case CRG_STEP_HEUN_1: {
+        const float d = (xv - den) / a.sigma;
+        const float x2 = xv + a.dt * d;
+        if (a.one_call) {
+          xn = x2;
+        } else {
+          a.x2[i] = x2;
+          a.d[i] = d;
+          store_x = false;
+        }
+        break;
+      }
+      case CRG_STEP_HEUN_2: {
+        const float d2 = (xin - den) / a.sigma;
+        const float dp = (a.d[i] + d2) / 2.0f;
+        xn = xv + dp * a.dt;
+        break;
+      }
+      case CRG_STEP_DPMPP2S_1:
+        if (!a.one_call) {
+          a.x2[i] = a.m[0] * xv - a.m[1] * den;
+          store_x = false;
+          break;
+        }
+        [[fallthrough]];
+      case CRG_STEP_EULER_A: {
+        const float d = (xv - den) / a.sigma;
+        xn = xv + a.dt * d;
+        noised = true;
+        break;
+      }
+      case CRG_STEP_DPMPP2S_2:
+        xn = a.m[2] * xv - a.m[3] * den;
+        noised = true;
+        break;
+      case CRG_STEP_LMS: {
+        const float d = (xv - den) / a.sigma;
+        a.d[i] = d;
+        float acc = a.coef[0] * d;
+        for (int k = 0; k < a.n_hist; ++k) acc = acc + a.coef[k + 1] * a.hist[k][i];
+        xn = xv + acc;
+        break;
+      }
+      default:
+        break;
+    }
+    if (noised && a.add_noise) xn = xn + (a.noise[i] * a.s_noise) * a.sigma_up;
+    if (store_x) a.x[i] = xn;
+  }
+}
+}  // namespace
+
+extern "C" int crg_cfg_sampler_step(crg_ctx* ctx, void* stream, const crg_sampler_step_args* args) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, args != nullptr, "cfg_sampler_step: null args");
+  const crg_sampler_step_args& a = *args;
+  const int k = a.kind;
+  CRG_REQUIRE(ctx, k >= CRG_STEP_EULER_A && k <= CRG_STEP_LMS, "cfg_sampler_step: unknown kind %d", k);
+  CRG_REQUIRE(ctx, a.n > 0 && a.x && a.eps, "cfg_sampler_step: empty input");
+  const bool two_call_first = (k == CRG_STEP_HEUN_1 || k == CRG_STEP_DPMPP2S_1) && !a.one_call;
+  const bool divides = k == CRG_STEP_EULER_A || k == CRG_STEP_HEUN_1 || k == CRG_STEP_HEUN_2 || k == CRG_STEP_LMS ||
+                       (k == CRG_STEP_DPMPP2S_1 && a.one_call);
+  const bool may_noise = k == CRG_STEP_EULER_A || k == CRG_STEP_DPMPP2S_2 || (k == CRG_STEP_DPMPP2S_1 && a.one_call);
+  CRG_REQUIRE(ctx, !divides || a.sigma > 0.f, "cfg_sampler_step: kind %d divides by sigma, which must be positive (got %g)", k,
+              (double)a.sigma);
+  CRG_REQUIRE(ctx, !(two_call_first || k == CRG_STEP_HEUN_2 || k == CRG_STEP_DPMPP2S_2) || a.x2, "cfg_sampler_step: kind %d needs x2", k);
+  CRG_REQUIRE(ctx, !((k == CRG_STEP_HEUN_1 && !a.one_call) || k == CRG_STEP_HEUN_2 || k == CRG_STEP_LMS) || a.d,
+              "cfg_sampler_step: kind %d needs d", k);
+  CRG_REQUIRE(ctx, !may_noise || !a.add_noise || a.noise, "cfg_sampler_step: add_noise needs a noise tensor");
+  if (k == CRG_STEP_LMS) {
+    CRG_REQUIRE(ctx, a.n_hist >= 0 && a.n_hist <= 3, "cfg_sampler_step: n_hist %d out of 0..3", a.n_hist);
+    for (int h = 0; h < a.n_hist; ++h) CRG_REQUIRE(ctx, a.hist[h] != nullptr, "cfg_sampler_step: hist[%d] is null", h);
+  }
+  crg_sampler_step_args kargs = a;
+  if (!may_noise || !kargs.add_noise) {  // nothing noise-related is read
+    kargs.add_noise = 0;
+    kargs.noise = nullptr;
+  }
+  if (k != CRG_STEP_LMS) kargs.n_hist = 0;
+  hipStream_t st = (hipStream_t)stream;
+  // x, both eps halves and one store, plus what the kind adds
+  const double words = 4.0 + (k == CRG_STEP_HEUN_1 && two_call_first ? 1.0 : 0.0) + (k == CRG_STEP_HEUN_2 ? 2.0 : 0.0) +
+                       (k == CRG_STEP_DPMPP2S_2 ? 1.0 : 0.0) + (k == CRG_STEP_LMS ? 1.0 + kargs.n_hist : 0.0) + (kargs.add_noise ? 1.0 : 0.0);
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, 12.0 * a.n, 4.0 * a.n * words);
+  hipLaunchKernelGGL(cfg_sampler_step_kernel, dim3(grid_for(a.n)), dim3(256), 0, st, kargs);
+  CRG_CHECK_LAUNCH(ctx, "cfg_sampler_step");
+  return 0;
+}
+
 extern "C" int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, n > 0, "axpby: empty");

@@ -1104,6 +1104,43 @@ def cfg_dpmpp2m_step_(x: torch.Tensor, eps2: torch.Tensor, old_den: torch.Tensor
     return _written(x)
 
 
+STEP_KINDS = {"euler_a": L.STEP_EULER_A, "heun_1": L.STEP_HEUN_1, "heun_2": L.STEP_HEUN_2, "dpmpp2s_1": L.STEP_DPMPP2S_1,
+              "dpmpp2s_2": L.STEP_DPMPP2S_2, "lms": L.STEP_LMS}
+
+
+def cfg_sampler_step_(kind: str, x: torch.Tensor, eps2: torch.Tensor, c_out: float, cfg_scale: float, sigma: float = 0.0, dt: float = 0.0,
+                      x2: Optional[torch.Tensor] = None, d: Optional[torch.Tensor] = None, hist=(), noise: Optional[torch.Tensor] = None,
+                      sigma_up: float = 0.0, s_noise: float = 1.0, m=(0.0, 0.0, 0.0, 0.0), coef=(0.0, 0.0, 0.0, 0.0), one_call: bool = False,
+                      add_noise: bool = False) -> torch.Tensor:
+    """In-place fused k-sampler evaluation step (crg_cfg_sampler_step, one launch): `kind` one of STEP_KINDS; x fp32 [b, ...], eps2
+    fp32 [2b, ...] (the raw network output, uncond half first); x2 / d / hist / noise fp32 [b, ...] as the kind reads or writes them
+    (see include/crg_hip.h); the scalars are the fp32 values the reference's per-step tensors hold.  Returns x."""
+    bufs = [x2, d, noise] + list(hist)
+    _need_cuda(x, eps2, *bufs)
+    if kind not in STEP_KINDS or len(hist) > 3:
+        raise L.CrgError(f"cfg_sampler_step_: unknown kind {kind!r} or more than 3 history buffers")
+    if x.dtype != torch.float32 or eps2.dtype != torch.float32 or not x.is_contiguous() or not eps2.is_contiguous() \
+            or eps2.numel() != 2 * x.numel() or any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                                                                       or t.numel() != x.numel()) for t in bufs):
+        raise L.CrgError("cfg_sampler_step_: contiguous fp32 x [b,...], eps [2b,...] and [b,...] side buffers expected")
+    a = L.SamplerStepArgs()
+    a.kind, a.n = STEP_KINDS[kind], x.numel()
+    a.x, a.eps, a.x2, a.d, a.noise = _p(x), _p(eps2), _p(x2), _p(d), _p(noise)
+    for k, t in enumerate(hist):
+        a.hist[k] = _p(t)
+    a.c_out, a.cfg_scale, a.sigma, a.dt, a.sigma_up, a.s_noise = (float(v) for v in (c_out, cfg_scale, sigma, dt, sigma_up, s_noise))
+    m, coef = list(m) + [0.0] * (4 - len(m)), list(coef) + [0.0] * (4 - len(coef))
+    for k in range(4):
+        a.m[k], a.coef[k] = float(m[k]), float(coef[k])
+    a.n_hist, a.one_call, a.add_noise = len(hist), 1 if one_call else 0, 1 if add_noise else 0
+    h = _h(x)
+    L.check(L.load().crg_cfg_sampler_step(h, _st(), C.byref(a)), h, "crg_cfg_sampler_step")
+    for t in (x2, d):
+        if t is not None:
+            _written(t)
+    return _written(x)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

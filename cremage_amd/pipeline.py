@@ -274,15 +274,19 @@ def build_synthetic_sdxl_refiner(unet_cfg=None, vae_dd=None, device="cuda", unet
 
 @torch.no_grad()
 def txt2img_sdxl(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
-                 x0: Optional[torch.Tensor] = None, decode: bool = True, sampler: str = "euler_edm", stage2strength: Optional[float] = None):
+                 x0: Optional[torch.Tensor] = None, decode: bool = True, sampler: str = "euler_edm", stage2strength: Optional[float] = None,
+                 discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
     """run_txt2img -> do_sample (modules/sdxl/sdxl_pipeline/sdxl_image_generator_utils.py:559-772): randn [b,4,H/8,W/8]
     (:695), sampler(denoiser, randn, cond=c, uc=uc) (:707), decode_first_stage in fp32 (:727-734), clamp((x+1)/2, 0, 1).
-    c / uc: {"crossattn": [b,77,2048], "vector": [b,2816]}.  `sampler`: "euler_edm" or "dpmpp2m"; `stage2strength`: the refiner
-    strength of a two-stage run, whose base stage stops early (Txt2NoisyDiscretizationWrapper)."""
+    c / uc: {"crossattn": [b,77,2048], "vector": [b,2816]}.  `sampler`: a key of sgm_hip.sampling.SGM_SAMPLERS or Cremage's name for
+    it ("HeunEDM", ...); `stage2strength`: the refiner strength of a two-stage run, whose base stage stops early
+    (Txt2NoisyDiscretizationWrapper); `discretization`: "legacy_ddpm" or "edm"; `sampler_options`: Cremage's sampler preferences
+    (sgm_hip.sampling.SAMPLER_OPTION_DEFAULTS)."""
     b = c["crossattn"].shape[0]
     if x0 is None:
         x0 = torch.randn((b, 4, height // 8, width // 8), device=c["crossattn"].device)
-    samples = eng.sample(x0, c, uc, steps, cfg_scale, sampler=sampler, stage2strength=stage2strength)
+    samples = eng.sample(x0, c, uc, steps, cfg_scale, sampler=sampler, stage2strength=stage2strength, discretization=discretization,
+                         options=sampler_options)
     if not decode:
         return None, samples
     x = eng.decode_first_stage(samples)
@@ -292,12 +296,13 @@ def txt2img_sdxl(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 
 @torch.no_grad()
 def img2img_sdxl(eng, init_image: torch.Tensor, c: dict, uc: dict, *, steps: int = 30, strength: float = 0.3, cfg_scale: float = 5.0,
                  enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, decode: bool = True,
-                 sampler: str = "euler_edm", stage2strength: Optional[float] = None):
+                 sampler: str = "euler_edm", stage2strength: Optional[float] = None, discretization: str = "legacy_ddpm",
+                 sampler_options: Optional[dict] = None):
     """run_img2img -> do_img2img (sdxl_image_generator_utils.py:775-1025); with strength 0.3 on a face crop this is the second
     pass of the auto-face-fix (modules/sdxl/face_img2img... -> the same do_img2img).  init_image [b,3,H,W] in [-1,1].
-    `sampler` / `stage2strength` as in txt2img_sdxl."""
+    `sampler` / `stage2strength` / `discretization` / `sampler_options` as in txt2img_sdxl."""
     samples = eng.img2img(init_image, c, uc, steps, strength, cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise, sampler=sampler,
-                          stage2strength=stage2strength)
+                          stage2strength=stage2strength, discretization=discretization, options=sampler_options)
     if not decode:
         return None, samples
     x = eng.decode_first_stage(samples)
@@ -306,11 +311,13 @@ def img2img_sdxl(eng, init_image: torch.Tensor, c: dict, uc: dict, *, steps: int
 
 @torch.no_grad()
 def refine_sdxl(refiner, z: torch.Tensor, c2: dict, uc2: dict, *, steps: int, strength: float, cfg_scale: float, sampler: str = "dpmpp2m",
-                decode: bool = True):
+                decode: bool = True, discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
     """The refiner stage on base latents z [b,4,H/8,W/8] (apply_refiner, sdxl_image_generator.py:307-347): Img2Img-pruned schedule
     of `steps` at `strength`, no added noise, then decode and clamp((x+1)/2, 0, 1).  c2 / uc2: the refiner conditioner's output,
-    {"crossattn": [b,77,1280], "vector": [b,2560]}.  Returns (images or None, latents)."""
-    samples = refiner.refine(z, c2, uc2, steps, strength, cfg_scale, sampler=sampler)
+    {"crossattn": [b,77,1280], "vector": [b,2560]}.  `sampler` / `discretization` / `sampler_options` as in txt2img_sdxl.  Returns
+    (images or None, latents)."""
+    samples = refiner.refine(z, c2, uc2, steps, strength, cfg_scale, sampler=sampler, discretization=discretization,
+                             options=sampler_options)
     if not decode:
         return None, samples
     x = refiner.decode_first_stage(samples)
@@ -320,26 +327,29 @@ def refine_sdxl(refiner, z: torch.Tensor, c2: dict, uc2: dict, *, steps: int, st
 @torch.no_grad()
 def txt2img_sdxl_refined(base, refiner, c: dict, uc: dict, c2: dict, uc2: dict, *, steps: int = 30, refiner_strength: float = 0.15,
                          cfg_scale: float = 5.0, sampler: str = "dpmpp2m", height: int = 1024, width: int = 1024,
-                         x0: Optional[torch.Tensor] = None, decode: bool = True):
+                         x0: Optional[torch.Tensor] = None, decode: bool = True, discretization: str = "legacy_ddpm",
+                         sampler_options: Optional[dict] = None):
     """SDXL txt2img with the refiner stage (sdxl_use_refiner, sdxl_image_generator.py:420-424, :555-635): the base samples with the
     schedule's last sigmas dropped (Txt2Noisy, stage2strength = refiner_strength) and is not decoded; the refiner continues from its
     latents (refine_sdxl) and its first stage decodes.  refiner_strength == 0 turns the refiner off, as the reference does: the
-    result is txt2img_sdxl's.  Returns (images or None, base latents, final latents)."""
+    result is txt2img_sdxl's.  Both stages use `sampler`, `discretization` and `sampler_options` (as in txt2img_sdxl).  Returns
+    (images or None, base latents, final latents)."""
+    smp = dict(sampler=sampler, discretization=discretization, sampler_options=sampler_options)
     if refiner_strength == 0:
         images, samples = txt2img_sdxl(base, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, decode=decode,
-                                       sampler=sampler)
+                                       **smp)
         return images, samples, samples
-    _, z = txt2img_sdxl(base, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, decode=False, sampler=sampler,
-                        stage2strength=refiner_strength)
-    images, samples = refine_sdxl(refiner, z, c2, uc2, steps=steps, strength=refiner_strength, cfg_scale=cfg_scale, sampler=sampler,
-                                  decode=decode)
+    _, z = txt2img_sdxl(base, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, decode=False,
+                        stage2strength=refiner_strength, **smp)
+    images, samples = refine_sdxl(refiner, z, c2, uc2, steps=steps, strength=refiner_strength, cfg_scale=cfg_scale, decode=decode, **smp)
     return images, z, samples
 
 
 @torch.no_grad()
 def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
                          fix_size: Optional[int] = None, strength: float = 0.3, x0: Optional[torch.Tensor] = None,
-                         enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, paste: bool = True):
+                         enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, paste: bool = True,
+                         sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
     """BASELINE config 5: SDXL txt2img, then the auto-face-fix second pass on one region per image - the UNet RE-ENTRY on a crop.
 
     Reference flow (modules/sdxl/sdxl_pipeline/sdxl_image_generator_utils.py:559-772 txt2img, then per detected face
@@ -349,14 +359,16 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
     In scope here is the numeric path (both UNet passes, VAE encode / decode); the glue around it is deliberately plain PyTorch:
     `boxes` = one (top, left, size) per image instead of the face detector (out of scope), the two resizes are
     F.interpolate(bilinear, antialias off) instead of cv2 Lanczos (not built), the paste is a hard-edged copy.
+    Both passes use `sampler`, `discretization` and `sampler_options` (as in txt2img_sdxl).
     Returns (final images [b,3,H,W] in [0,1], first-pass images, second-pass crops at `fix_size`)."""
     import torch.nn.functional as F
-    first, _ = txt2img_sdxl(eng, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0)
+    smp = dict(sampler=sampler, discretization=discretization, sampler_options=sampler_options)
+    first, _ = txt2img_sdxl(eng, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, **smp)
     fix = fix_size or height
     crops = torch.stack([F.interpolate(first[i:i + 1, :, t:t + sz, l:l + sz], size=(fix, fix), mode="bilinear", align_corners=False)[0]
                          for i, (t, l, sz) in enumerate(boxes)])
     fixed, _ = img2img_sdxl(eng, crops * 2.0 - 1.0, c, uc, steps=steps, strength=strength, cfg_scale=cfg_scale, enc_noise=enc_noise,
-                            fwd_noise=fwd_noise)
+                            fwd_noise=fwd_noise, **smp)
     out = first.clone()
     if paste:
         for i, (t, l, sz) in enumerate(boxes):
@@ -366,12 +378,14 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
 
 @torch.no_grad()
 def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps: int = 30, strength: float = 0.3, cfg_scale: float = 5.0,
-                  target_edge_len: int = 1024, enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None):
+                  target_edge_len: int = 1024, enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None,
+                  sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
     """The auto-face-fix second pass with the REFERENCE's host-side glue (cremage_amd.postprocess: buffer / clamp / aspect-preserving
     Lanczos resize / white padding / un-pad / resize back / paste, face_detector_engine.py:152-288) around the UNet re-entry
     (`img2img_sdxl`, strength 0.3).  images [b,3,H,W] in [0,1]; faces[i] = list of (x, y, w, h) boxes of image i (the detector is out
     of scope).  Differences from the reference that remain: plain paste instead of cv.seamlessClone (no OpenCV here), and one
-    conditioning row per image instead of a gender-prefixed prompt.  Returns [b,3,H,W] in [0,1] on the images' device."""
+    conditioning row per image instead of a gender-prefixed prompt.  `sampler` / `discretization` / `sampler_options` as in
+    txt2img_sdxl.  Returns [b,3,H,W] in [0,1] on the images' device."""
     from . import postprocess as PP
     out = []
     for i in range(images.shape[0]):
@@ -381,7 +395,8 @@ def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps:
         def i2i(x):
             y, _ = img2img_sdxl(eng, x.to(images.device), ci, uci, steps=steps, strength=strength, cfg_scale=cfg_scale,
                                 enc_noise=enc_noise[i:i + 1] if enc_noise is not None else None,
-                                fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None)
+                                fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None, sampler=sampler,
+                                discretization=discretization, sampler_options=sampler_options)
             return y
         pil = PP.face_fix(PP.unit_tensor_to_pil(images[i]), faces[i], i2i, target_edge_len)
         out.append((PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5)

@@ -1,10 +1,11 @@
 """SDXL denoiser / guider / sampler glue - stays on PyTorch (north_star), behaviour of
 modules/sdxl/sgm/modules/diffusionmodules/{denoiser.py:10-75, denoiser_scaling.py:29-37, discretizer.py:17-78,
-guiders.py:24-65, sampling.py:29-219,309-318, wrappers.py:24-34} and DiffusionEngine.decode_first_stage
+guiders.py:24-65, sampling.py:29-573, sampling_utils.py:7-51, wrappers.py:24-34} and DiffusionEngine.decode_first_stage
 (sgm/models/diffusion.py:118-136).  Tensors here are [b, 4, L, L] latents and per-sample scalars; the per-step cost
 is the UNet call."""
 from __future__ import annotations
 
+import functools
 from typing import Dict, Optional
 
 import numpy as np
@@ -37,6 +38,54 @@ class LegacyDDPMDiscretization:
         sigmas = self.get_sigmas(n, device=device)
         sigmas = append_zero(sigmas) if do_append_zero else sigmas
         return sigmas if not flip else torch.flip(sigmas, (0,))
+
+
+class EDMDiscretization:
+    """discretizer.py:28-48 (+ Discretization.__call__ :17-24): the Karras et al. schedule.  Always computed on the CPU in fp32 with
+    the reference's torch expression, then moved to `device`, so a run's sigmas equal those of a CPU run of the reference bit for
+    bit whatever the device."""
+
+    def __init__(self, sigma_min=0.002, sigma_max=80.0, rho=7.0):
+        self.sigma_min = sigma_min
+        self.sigma_max = sigma_max
+        self.rho = rho
+
+    def get_sigmas(self, n, device="cpu"):
+        ramp = torch.linspace(0, 1, n)
+        min_inv_rho = self.sigma_min ** (1 / self.rho)
+        max_inv_rho = self.sigma_max ** (1 / self.rho)
+        sigmas = (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** self.rho
+        return sigmas.to(device)
+
+    def __call__(self, n, do_append_zero=True, device="cpu", flip=False):
+        sigmas = self.get_sigmas(n, device=device)
+        sigmas = append_zero(sigmas) if do_append_zero else sigmas
+        return sigmas if not flip else torch.flip(sigmas, (0,))
+
+
+# Cremage's sampler preferences (cremage/configs/preferences.py:149-165) and what they default to
+SAMPLER_OPTION_DEFAULTS = {"sampler_s_churn": 0.0, "sampler_s_tmin": 0.0, "sampler_s_tmax": 999.0, "sampler_s_noise": 1.0,
+                           "sampler_eta": 1.0, "sampler_order": 4, "discretization_sigma_min": 0.0292, "discretization_sigma_max": 14.6146,
+                           "discretization_rho": 3.0}
+DISCRETIZATIONS = {"legacy_ddpm": "legacy_ddpm", "LegacyDDPMDiscretization": "legacy_ddpm", "edm": "edm", "EDMDiscretization": "edm"}
+
+
+def sampler_options(options: Optional[Dict] = None) -> Dict:
+    """SAMPLER_OPTION_DEFAULTS overridden by `options` (keyed by the preference names); an unknown name is an error."""
+    unknown = set(options or {}) - set(SAMPLER_OPTION_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown sampler options {sorted(unknown)} (known: {sorted(SAMPLER_OPTION_DEFAULTS)})")
+    return dict(SAMPLER_OPTION_DEFAULTS, **(options or {}))
+
+
+def make_discretization(name: str = "legacy_ddpm", options: Optional[Dict] = None):
+    """get_discretization_config (sdxl_image_generator_utils.py:418-449): "legacy_ddpm" / "edm" (or Cremage's class names)."""
+    if name not in DISCRETIZATIONS:
+        raise ValueError(f"unknown discretization {name!r} (one of {sorted(DISCRETIZATIONS)})")
+    if DISCRETIZATIONS[name] == "legacy_ddpm":
+        return LegacyDDPMDiscretization()
+    o = sampler_options(options)
+    return EDMDiscretization(sigma_min=o["discretization_sigma_min"], sigma_max=o["discretization_sigma_max"], rho=o["discretization_rho"])
 
 
 class EpsScaling:
@@ -296,7 +345,345 @@ class DPMPP2MSampler:
         return x
 
 
-SGM_SAMPLERS = {"euler_edm": EulerEDMSampler, "dpmpp2m": DPMPP2MSampler}  # sdxl_image_generator_utils.py:451-511 "EulerEDMSampler", "DPMPP2MSampler"
+def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
+    """sampling_utils.py:22-39 (on the CPU fp32 [b] vectors of the schedule)."""
+    if not eta:
+        return sigma_to, torch.zeros_like(sigma_to)  # the reference returns a Python 0.0 here, which its append_dims rejects
+    sigma_up = torch.minimum(sigma_to, eta * (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5)
+    sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+    return sigma_down, sigma_up
+
+
+@functools.lru_cache(maxsize=None)
+def _gauss_legendre(n: int):
+    nodes, weights = np.polynomial.legendre.leggauss(n)
+    return tuple(float(v) for v in nodes), tuple(float(v) for v in weights)
+
+
+def linear_multistep_coeff(order: int, t, i: int, j: int) -> float:
+    """sampling_utils.py:7-19 without scipy: the integral of the Lagrange basis polynomial j (degree order - 1) over [t[i], t[i+1]] by
+    float64 Gauss-Legendre quadrature with `order` nodes, exact for that degree.  The reference's adaptive scipy.integrate.quad
+    evaluates its integrand in float32 (NumPy 2 keeps the float32 schedule's precision), so its coefficients and these differ in the
+    last fp32 bits (<= 3e-7 relative)."""
+    if order - 1 > i:
+        raise ValueError(f"Order {order} too high for step {i}")
+    nodes, weights = _gauss_legendre(max(order, 1))
+    a, b = float(t[i]), float(t[i + 1])
+    half, mid = 0.5 * (b - a), 0.5 * (b + a)
+    tj = float(t[i - j])
+    tk = [float(t[i - k]) for k in range(order) if k != j]
+    total = 0.0
+    for x, w in zip(nodes, weights):
+        tau = half * x + mid
+        prod = 1.0
+        for v in tk:
+            prod *= (tau - v) / (tj - v)
+        total += w * prod
+    return half * total
+
+
+def edm_table(sigmas: torch.Tensor, b: int, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf")):
+    """Per step of EDMSampler.__call__ / sampler_step (sampling.py:165-219, :332-358) over the CPU fp32 schedule, with the reference's
+    torch expressions on [b] vectors: dicts of Python floats holding fp32 values - sigma_hat, the churn noise's std (None when
+    gamma == 0: no draw), dt = next - sigma_hat, next, and two_call (HeunEDM's second evaluation, sum(next) >= 1e-14)."""
+    sigmas = sigmas.detach().to("cpu", torch.float32)
+    s_in, num = torch.ones([b]), len(sigmas)
+    rows = []
+    for i in range(num - 1):
+        sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
+        gamma = min(s_churn / (num - 1), 2 ** 0.5 - 1) if s_tmin <= sigmas[i] <= s_tmax else 0.0
+        sigma_hat = sigma * (gamma + 1.0)
+        churn = float(((sigma_hat ** 2 - sigma ** 2) ** 0.5)[0]) if gamma > 0 else None
+        rows.append(dict(sigma_hat=float(sigma_hat[0]), churn=churn, dt=float((nxt - sigma_hat)[0]), next=float(nxt[0]),
+                         two_call=not bool(torch.sum(nxt) < 1e-14)))
+    return rows
+
+
+def ancestral_table(sigmas: torch.Tensor, b: int, eta=1.0, multipliers: bool = True):
+    """Per step of AncestralSampler / DPMPP2SAncestralSampler (sampling.py:222-268, :384-456) over the CPU fp32 schedule, with the
+    reference's torch expressions on [b] vectors: sigma, next, sigma_down, sigma_up, dt = sigma_down - sigma, two_call (DPM++ 2S's
+    second evaluation, sum(sigma_down) >= 1e-14) and, on a two-call step with `multipliers`, DPM++ 2S's m1..m4 and its second
+    evaluation sigma to_sigma(s) (None otherwise)."""
+    sigmas = sigmas.detach().to("cpu", torch.float32)
+    s_in = torch.ones([b])
+    rows = []
+    for i in range(len(sigmas) - 1):
+        sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
+        down, up = get_ancestral_step(sigma, nxt, eta=eta)
+        two_call = not bool(torch.sum(down) < 1e-14)
+        m, s_sigma = None, None
+        if two_call and multipliers:
+            t, t_next = _to_neg_log_sigma(sigma), _to_neg_log_sigma(down)   # get_variables
+            h = t_next - t
+            s = t + 0.5 * h
+            m = [float(v[0]) for v in (_to_sigma(s) / _to_sigma(t), (-0.5 * h).expm1(), _to_sigma(t_next) / _to_sigma(t), (-h).expm1())]
+            s_sigma = float(_to_sigma(s)[0])
+        rows.append(dict(sigma=float(sigma[0]), next=float(nxt[0]), sigma_down=float(down[0]), sigma_up=float(up[0]),
+                         dt=float((down - sigma)[0]), two_call=two_call, m=m, s_sigma=s_sigma))
+    return rows
+
+
+def lms_table(sigmas: torch.Tensor, order: int):
+    """Per step of LinearMultistepSampler.__call__ (sampling.py:282-306): the coefficients, newest derivative first."""
+    t = sigmas.detach().to("cpu", torch.float32).tolist()
+    out = []
+    for i in range(len(t) - 1):
+        cur = min(i + 1, order)
+        out.append([linear_multistep_coeff(cur, t, i, j) for j in range(cur)])
+    return out
+
+
+def snap_to_table(table: torch.Tensor, sigmas: torch.Tensor) -> torch.Tensor:
+    """DiscreteDenoiser.sigma_to_idx (denoiser.py:54-56) of every sigma at once, on the CPU: the index of the nearest table entry."""
+    return (sigmas - table[:, None]).abs().argmin(dim=0)
+
+
+class _FusedEvals:
+    """The fused path's denoiser inputs for a run's evaluation sigmas `ev` (CPU fp32, in call order): DiscreteDenoiser.sigma_to_idx
+    for all of them at once, the snapped sigmas (c_out = -sq), c_in with the per-call path's device arithmetic and the timestep rows."""
+
+    def __init__(self, dd: "DiscreteDenoiser", network, ev: torch.Tensor, x: torch.Tensor, cc: Dict):
+        table = dd.sigmas.detach().cpu()
+        idx = snap_to_table(table, ev)
+        self.sq = [float(v) for v in table[idx]]
+        self.c_in = 1 / (table[idx].to(x.device) ** 2 + 1.0) ** 0.5
+        self.t_rows = idx.to(x.device).reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous()
+        self.network, self.cc, self.k = network, cc, 0
+
+    def __call__(self, xin: torch.Tensor):
+        """The next evaluation: one input build, the network; returns (eps [2b, ...], c_out)."""
+        k, self.k = self.k, self.k + 1
+        xx = torch.empty((2,) + tuple(xin.shape), dtype=xin.dtype, device=xin.device)
+        torch.mul(xin.unsqueeze(0).expand_as(xx), self.c_in[k], out=xx)
+        eps2 = self.network(xx.view((2 * xin.shape[0],) + tuple(xin.shape[1:])), self.t_rows[k], self.cc)
+        return eps2.contiguous(), -self.sq[k]
+
+
+class _KSampler:
+    """Shared plumbing of HeunEDM, EulerAncestral, DPM++ 2S ancestral and LMS: the schedule on the CPU (what steers the loop) and on
+    the device, prepare_sampling_loop's `x *= sqrt(1 + sigma_0^2)` on a copy, and the choice of path.  Fused path (CUDA fp32 latents,
+    VanillaCFG with scale != 1, the engine's denoiser and network as `parts`): per UNet evaluation one input build, the network and
+    one crg_cfg_sampler_step launch.  Otherwise the torch loop, which restates the reference and runs on the CPU as well."""
+
+    def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", fused: bool = True):
+        self.num_steps = num_steps
+        self.discretization = LegacyDDPMDiscretization()
+        self.guider = guider
+        self.device = device
+        self.fused = fused
+
+    def denoise(self, x, denoiser, sigma, cond, uc):
+        denoised = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))
+        return self.guider(denoised, sigma)
+
+    def fused_ok(self, x, parts) -> bool:
+        return (self.fused and parts is not None and x.is_cuda and x.dtype == torch.float32 and isinstance(self.guider, VanillaCFG)
+                and self.guider.scale != 1.0)
+
+    @torch.no_grad()
+    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, parts=None):
+        """`parts` = (DiscreteDenoiser, network): the pieces `denoiser` applies, for the fused path."""
+        n = self.num_steps if num_steps is None else num_steps
+        sh = self.discretization(n, device="cpu").float()
+        uc = cond if uc is None else uc
+        x = x * float(torch.sqrt(1.0 + sh[0] ** 2.0))
+        if self.fused_ok(x, parts):
+            return self._fused(parts[0], parts[1], x.contiguous(), cond, uc, sh)
+        return self._loop(denoiser, x, cond, uc, sh)
+
+    @staticmethod
+    def _sig(v: float, x):
+        """A [b] sigma vector on x's device holding the fp32 value v (s_in * sigma)."""
+        return torch.full((x.shape[0],), v, dtype=torch.float32, device=x.device)
+
+    @staticmethod
+    def _to_d(x, sigma, denoised):
+        return (x - denoised) / append_dims(sigma, x.ndim)  # sampling_utils.py:42-43
+
+
+class HeunEDMSampler(_KSampler):
+    """sampling.py:147-219,321-358: Heun steps on the EDM ODE, two UNet calls per step (one when the next sigma is 0), with the EDM
+    churn (s_churn > 0: noise drawn and added before the first call of the steps where gamma > 0)."""
+
+    def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0,
+                 fused: bool = True):
+        super().__init__(num_steps, guider, device, fused)
+        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
+
+    def _churn(self, x, r):
+        if r["churn"] is None:
+            return x
+        eps = torch.randn_like(x) * self.s_noise
+        return x + eps * r["churn"]
+
+    def _loop(self, denoiser, x, cond, uc, sh):
+        for r in edm_table(sh, x.shape[0], self.s_churn, self.s_tmin, self.s_tmax):
+            x = self._churn(x, r)
+            sigma_hat = self._sig(r["sigma_hat"], x)
+            denoised = self.denoise(x, denoiser, sigma_hat, cond, uc)
+            d = self._to_d(x, sigma_hat, denoised)
+            euler_step = x + r["dt"] * d
+            if not r["two_call"]:
+                x = euler_step
+                continue
+            nxt = self._sig(r["next"], x)
+            denoised = self.denoise(euler_step, denoiser, nxt, cond, uc)
+            d_new = self._to_d(euler_step, nxt, denoised)
+            d_prime = (d + d_new) / 2.0
+            x = x + d_prime * r["dt"]
+        return x
+
+    def _fused(self, dd, network, x, cond, uc, sh):
+        from .. import ops
+        rows = edm_table(sh, x.shape[0], self.s_churn, self.s_tmin, self.s_tmax)
+        ev = [v for r in rows for v in ([r["sigma_hat"], r["next"]] if r["two_call"] else [r["sigma_hat"]])]
+        evals = _FusedEvals(dd, network, torch.tensor(ev, dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
+        x2, d = torch.empty_like(x), torch.empty_like(x)
+        cfg = self.guider.scale
+        for r in rows:
+            x = self._churn(x, r).contiguous()
+            eps2, c_out = evals(x)
+            ops.cfg_sampler_step_("heun_1", x, eps2, c_out, cfg, sigma=r["sigma_hat"], dt=r["dt"], x2=x2, d=d, one_call=not r["two_call"])
+            if r["two_call"]:
+                eps2, c_out = evals(x2)
+                ops.cfg_sampler_step_("heun_2", x, eps2, c_out, cfg, sigma=r["next"], dt=r["dt"], x2=x2, d=d)
+        return x
+
+
+class _AncestralSampler(_KSampler):
+    """sampling.py:222-268: eta, s_noise, and one torch.randn_like(x) per step - the last step's included, which the reference's
+    torch.where throws away."""
+
+    def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", eta=1.0, s_noise=1.0, fused: bool = True):
+        super().__init__(num_steps, guider, device, fused)
+        self.eta, self.s_noise = eta, s_noise
+
+    def _ancestral_step(self, x, r):
+        noise = torch.randn_like(x)
+        return x + noise * self.s_noise * r["sigma_up"] if r["next"] > 0.0 else x
+
+
+class EulerAncestralSampler(_AncestralSampler):
+    """sampling.py:361-381: an Euler step to sigma_down, then noise of std sigma_up."""
+
+    def _loop(self, denoiser, x, cond, uc, sh):
+        for r in ancestral_table(sh, x.shape[0], self.eta, multipliers=False):
+            sigma = self._sig(r["sigma"], x)
+            denoised = self.denoise(x, denoiser, sigma, cond, uc)
+            x = x + r["dt"] * self._to_d(x, sigma, denoised)
+            x = self._ancestral_step(x, r)
+        return x
+
+    def _fused(self, dd, network, x, cond, uc, sh):
+        from .. import ops
+        rows = ancestral_table(sh, x.shape[0], self.eta, multipliers=False)
+        evals = _FusedEvals(dd, network, torch.tensor([r["sigma"] for r in rows], dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
+        for r in rows:
+            eps2, c_out = evals(x)
+            noise = torch.randn_like(x)
+            ops.cfg_sampler_step_("euler_a", x, eps2, c_out, self.guider.scale, sigma=r["sigma"], dt=r["dt"], noise=noise,
+                                  sigma_up=r["sigma_up"], s_noise=self.s_noise, add_noise=r["next"] > 0.0)
+        return x
+
+
+class DPMPP2SAncestralSampler(_AncestralSampler):
+    """sampling.py:384-456: DPM++ 2S ancestral - a second UNet call at the midpoint sigma to_sigma(s) (off the denoiser's grid: it is
+    snapped for the scalings only), then noise of std sigma_up; a step whose sigma_down is 0 makes one call (the Euler step)."""
+
+    def _loop(self, denoiser, x, cond, uc, sh):
+        for r in ancestral_table(sh, x.shape[0], self.eta):
+            sigma = self._sig(r["sigma"], x)
+            denoised = self.denoise(x, denoiser, sigma, cond, uc)
+            if not r["two_call"]:
+                x = x + r["dt"] * self._to_d(x, sigma, denoised)
+            else:
+                m1, m2, m3, m4 = r["m"]
+                x2 = m1 * x - m2 * denoised
+                denoised2 = self.denoise(x2, denoiser, self._sig(r["s_sigma"], x), cond, uc)
+                x = m3 * x - m4 * denoised2
+            x = self._ancestral_step(x, r)
+        return x
+
+    def _fused(self, dd, network, x, cond, uc, sh):
+        from .. import ops
+        rows = ancestral_table(sh, x.shape[0], self.eta)
+        ev = [v for r in rows for v in ([r["sigma"], r["s_sigma"]] if r["two_call"] else [r["sigma"]])]
+        evals = _FusedEvals(dd, network, torch.tensor(ev, dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
+        x2 = torch.empty_like(x)
+        cfg = self.guider.scale
+        for r in rows:
+            eps2, c_out = evals(x)
+            noisy = dict(sigma_up=r["sigma_up"], s_noise=self.s_noise, add_noise=r["next"] > 0.0)
+            if not r["two_call"]:
+                ops.cfg_sampler_step_("dpmpp2s_1", x, eps2, c_out, cfg, sigma=r["sigma"], dt=r["dt"], noise=torch.randn_like(x),
+                                      one_call=True, **noisy)
+                continue
+            ops.cfg_sampler_step_("dpmpp2s_1", x, eps2, c_out, cfg, x2=x2, m=r["m"])
+            eps2, c_out = evals(x2)
+            ops.cfg_sampler_step_("dpmpp2s_2", x, eps2, c_out, cfg, x2=x2, m=r["m"], noise=torch.randn_like(x), **noisy)
+        return x
+
+
+class LinearMultistepSampler(_KSampler):
+    """sampling.py:271-306: linear multistep of the given order over the last derivatives (coefficients: lms_table).  The fused path
+    keeps the derivatives in a ring of `order` device buffers and covers order <= 4; a larger order runs the torch loop."""
+
+    FUSED_MAX_ORDER = 4
+
+    def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", order=4, fused: bool = True):
+        super().__init__(num_steps, guider, device, fused)
+        if int(order) < 1:
+            raise ValueError(f"LMS order must be >= 1 (got {order})")
+        self.order = int(order)
+
+    def fused_ok(self, x, parts) -> bool:
+        return self.order <= self.FUSED_MAX_ORDER and super().fused_ok(x, parts)
+
+    def _loop(self, denoiser, x, cond, uc, sh):
+        ds = []
+        for i, coeffs in enumerate(lms_table(sh, self.order)):
+            sigma = self._sig(float(sh[i]), x)
+            denoised = self.denoise(x, denoiser, sigma, cond, uc)
+            ds.append(self._to_d(x, sigma, denoised))
+            if len(ds) > self.order:
+                ds.pop(0)
+            x = x + sum(coeff * d for coeff, d in zip(coeffs, reversed(ds)))
+        return x
+
+    def _fused(self, dd, network, x, cond, uc, sh):
+        from .. import ops
+        table = lms_table(sh, self.order)
+        evals = _FusedEvals(dd, network, sh[:-1].clone(), x, self.guider.cat_cond(cond, uc))
+        ring = [torch.empty_like(x) for _ in range(self.order)]
+        for i, coeffs in enumerate(table):
+            eps2, c_out = evals(x)
+            hist = [ring[(i - k) % self.order] for k in range(1, len(coeffs))]
+            ops.cfg_sampler_step_("lms", x, eps2, c_out, self.guider.scale, sigma=float(sh[i]), d=ring[i % self.order], hist=hist,
+                                  coef=coeffs)
+        return x
+
+
+SGM_SAMPLERS = {"euler_edm": EulerEDMSampler, "dpmpp2m": DPMPP2MSampler, "heun_edm": HeunEDMSampler,
+                "euler_ancestral": EulerAncestralSampler, "dpmpp2s_ancestral": DPMPP2SAncestralSampler,
+                "linear_multistep": LinearMultistepSampler}  # get_sampler, sdxl_image_generator_utils.py:451-522
+# Cremage's SDXL sampler menu (modules/sdxl/const/const.py:37-45; init_sampling appends "Sampler") -> SGM_SAMPLERS keys
+CREMAGE_SAMPLER_KEYS = {"EulerEDM": "euler_edm", "HeunEDM": "heun_edm", "EulerAncestral": "euler_ancestral",
+                        "DPMPP2SAncestral": "dpmpp2s_ancestral", "DPMPP2M": "dpmpp2m", "LinearMultistep": "linear_multistep"}
+CREMAGE_SAMPLER_KEYS.update({k + "Sampler": v for k, v in list(CREMAGE_SAMPLER_KEYS.items())})
+# the options each sampler takes (get_sampler): constructor argument <- preference name
+_SAMPLER_OPTION_ARGS = {"euler_edm": dict(s_churn="sampler_s_churn", s_tmin="sampler_s_tmin", s_tmax="sampler_s_tmax", s_noise="sampler_s_noise"),
+                        "heun_edm": dict(s_churn="sampler_s_churn", s_tmin="sampler_s_tmin", s_tmax="sampler_s_tmax", s_noise="sampler_s_noise"),
+                        "euler_ancestral": dict(eta="sampler_eta", s_noise="sampler_s_noise"),
+                        "dpmpp2s_ancestral": dict(eta="sampler_eta", s_noise="sampler_s_noise"),
+                        "dpmpp2m": {}, "linear_multistep": dict(order="sampler_order")}
+
+
+def sampler_key(name: str) -> str:
+    """An SGM_SAMPLERS key, or Cremage's name for it ("HeunEDM", "HeunEDMSampler", ...), -> the key."""
+    key = CREMAGE_SAMPLER_KEYS.get(name, name)
+    if key not in SGM_SAMPLERS:
+        raise ValueError(f"unknown SDXL sampler {name!r} (one of {sorted(SGM_SAMPLERS)} or {sorted(CREMAGE_SAMPLER_KEYS)})")
+    return key
 
 
 class DiffusionEngine(nn.Module):
@@ -320,29 +707,34 @@ class DiffusionEngine(nn.Module):
         return self.scale_factor * self.first_stage_model.encode(x).sample(noise)
 
     def make_sampler(self, sampler: str, steps: int, cfg_scale: float, device, img2img_strength: Optional[float] = None,
-                     stage2strength: Optional[float] = None):
-        """init_sampling (sdxl_image_generator_utils.py:359-415) for the LegacyDDPM discretization and VanillaCFG."""
-        if sampler not in SGM_SAMPLERS:
-            raise ValueError(f"unknown SDXL sampler {sampler!r} (one of {sorted(SGM_SAMPLERS)})")
-        smp = SGM_SAMPLERS[sampler](steps, VanillaCFG(cfg_scale), device=device)
-        smp.discretization = wrap_discretization(smp.discretization, steps, img2img_strength, stage2strength)
+                     stage2strength: Optional[float] = None, discretization: str = "legacy_ddpm", options: Optional[Dict] = None):
+        """init_sampling (sdxl_image_generator_utils.py:359-415) for VanillaCFG: `sampler` an SGM_SAMPLERS key or Cremage's name
+        (CREMAGE_SAMPLER_KEYS), `discretization` "legacy_ddpm" or "edm", `options` Cremage's sampler / discretization preferences
+        (SAMPLER_OPTION_DEFAULTS; each sampler takes the ones get_sampler hands it)."""
+        key = sampler_key(sampler)
+        opts = sampler_options(options)
+        kwargs = {arg: opts[pref] for arg, pref in _SAMPLER_OPTION_ARGS[key].items()}
+        smp = SGM_SAMPLERS[key](steps, VanillaCFG(cfg_scale), device=device, **kwargs)
+        smp.discretization = wrap_discretization(make_discretization(discretization, opts), steps, img2img_strength, stage2strength)
         return smp
 
     def run_sampler(self, smp, x, cond: Dict, uc: Dict):
         """sampler(denoiser, x, cond=c, uc=uc) (sdxl_image_generator_utils.py:703-707, :1016)."""
         denoiser = lambda inp, sigma, c: self.denoiser(self.model, inp, sigma, c)  # noqa: E731
-        if isinstance(smp, DPMPP2MSampler):
+        if isinstance(smp, (DPMPP2MSampler, _KSampler)):
             return smp(denoiser, x, cond=cond, uc=uc, parts=(self.denoiser, self.model))
         return smp(denoiser, x, cond=cond, uc=uc)
 
     @torch.no_grad()
     def img2img(self, img, cond: Dict, uc: Dict, steps: int, strength: float, cfg_scale: float, enc_noise=None, fwd_noise=None,
-                sampler: str = "euler_edm", stage2strength: Optional[float] = None):
+                sampler: str = "euler_edm", stage2strength: Optional[float] = None, discretization: str = "legacy_ddpm",
+                options: Optional[Dict] = None):
         """do_img2img, sdxl_image_generator_utils.py:989-1016 (the face-fix re-entry of BASELINE config 5 is this call on a crop,
         strength 0.3): encode, noise to sigma_0 of the pruned schedule, sample over the remaining sigmas.  `stage2strength`: the
-        base stage of a refined run (Txt2Noisy around the Img2Img pruning)."""
+        base stage of a refined run (Txt2Noisy around the Img2Img pruning); `discretization` / `options` as in make_sampler."""
         z = self.encode_first_stage(img, enc_noise)
-        smp = self.make_sampler(sampler, steps, cfg_scale, z.device, img2img_strength=strength, stage2strength=stage2strength)
+        smp = self.make_sampler(sampler, steps, cfg_scale, z.device, img2img_strength=strength, stage2strength=stage2strength,
+                                discretization=discretization, options=options)
         sigmas = smp.discretization(steps, device=z.device)
         noise = torch.randn_like(z) if fwd_noise is None else fwd_noise
         noised_z = (z + noise * sigmas[0]) / torch.sqrt(1.0 + sigmas[0] ** 2.0)
@@ -350,18 +742,21 @@ class DiffusionEngine(nn.Module):
 
     @torch.no_grad()
     def sample(self, x, cond: Dict, uc: Dict, steps: int, cfg_scale: float, sampler: str = "euler_edm",
-               stage2strength: Optional[float] = None):
+               stage2strength: Optional[float] = None, discretization: str = "legacy_ddpm", options: Optional[Dict] = None):
         """do_sample, sdxl_image_generator_utils.py:695-707: sampler(denoiser, randn, cond=c, uc=uc).  `stage2strength`: the base
-        stage of a refined run, which stops early (Txt2NoisyDiscretizationWrapper)."""
-        smp = self.make_sampler(sampler, steps, cfg_scale, x.device, stage2strength=stage2strength)
+        stage of a refined run, which stops early (Txt2NoisyDiscretizationWrapper); `discretization` / `options` as in make_sampler."""
+        smp = self.make_sampler(sampler, steps, cfg_scale, x.device, stage2strength=stage2strength, discretization=discretization,
+                                options=options)
         return self.run_sampler(smp, x, cond, uc)
 
     @torch.no_grad()
-    def refine(self, z, cond: Dict, uc: Dict, steps: int, strength: float, cfg_scale: float, sampler: str = "dpmpp2m"):
+    def refine(self, z, cond: Dict, uc: Dict, steps: int, strength: float, cfg_scale: float, sampler: str = "dpmpp2m",
+               discretization: str = "legacy_ddpm", options: Optional[Dict] = None):
         """The refiner stage: apply_refiner (sdxl_image_generator.py:307-347) -> do_img2img with skip_encode and no added noise
         (sdxl_image_generator_utils.py:986-1016, finish_denoising is always True, sdxl_image_generator.py:566): the base latents
         divided by sqrt(1 + sigma_0^2) of the Img2Img-pruned schedule, then the sampler over that schedule."""
-        smp = self.make_sampler(sampler, steps, cfg_scale, z.device, img2img_strength=strength)
+        smp = self.make_sampler(sampler, steps, cfg_scale, z.device, img2img_strength=strength, discretization=discretization,
+                                options=options)
         sigmas = smp.discretization(smp.num_steps).to(z.device)
         noised_z = z / torch.sqrt(1.0 + sigmas[0] ** 2.0)
         return self.run_sampler(smp, noised_z, cond, uc)

@@ -368,6 +368,43 @@ int crg_cfg_ddim_step(crg_ctx* ctx, void* stream, void* x, const void* eps, cons
 int crg_cfg_dpmpp2m_step(crg_ctx* ctx, void* stream, void* x, const void* eps, void* old_den, int64_t n, float c_out, float cfg_scale,
                          float m1, float m2, float m3, float m4, int advanced);
 
+/* One fused evaluation step of the remaining SDXL k-samplers with classifier-free guidance (sgm sampling.py:147-456 HeunEDMSampler,
+ * EulerAncestralSampler, DPMPP2SAncestralSampler, :271-306 LinearMultistepSampler), in place, fp32, one rounding per operation in the
+ * reference's order.  Every kind first forms the guided denoised value of the evaluation's input xin (x, or x2 for the second call of
+ * a two-call step) from the raw network output eps ([2][n], unconditional half first):
+ *   den_h = eps_h * c_out + xin,   den = den_u + cfg_scale * (den_c - den_u)      DiscreteDenoiser (c_skip = 1), VanillaCFG
+ * then, with z = noise (read only when add_noise):
+ *   EULER_A     d = (x - den) / sigma;  x = x + dt * d  [+ (z * s_noise) * sigma_up]              dt = sigma_down - sigma
+ *   HEUN_1      d = (x - den) / sigma;  x2 = x + dt * d; writes x2 and d (one_call: x = x2)        sigma = sigma_hat, dt = next - sigma_hat
+ *   HEUN_2      d2 = (x2 - den) / sigma;  x = x + ((d + d2) / 2) * dt                               sigma = next sigma
+ *   DPMPP2S_1   x2 = m[0] * x - m[1] * den  (one_call: EULER_A's update and noise instead)
+ *   DPMPP2S_2   x = m[2] * x - m[3] * den  [+ (z * s_noise) * sigma_up]
+ *   LMS         d = (x - den) / sigma, written to d;  acc = coef[0] * d, acc = acc + coef[k] * hist[k - 1][i] (k < 1 + n_hist,
+ *               newest first);  x = x + acc
+ * A buffer a kind does not use on the step is not read (hist past n_hist, noise without add_noise, x2 / d on a one-call step). */
+enum { CRG_STEP_EULER_A = 0, CRG_STEP_HEUN_1 = 1, CRG_STEP_HEUN_2 = 2, CRG_STEP_DPMPP2S_1 = 3, CRG_STEP_DPMPP2S_2 = 4, CRG_STEP_LMS = 5 };
+typedef struct {
+  int kind;                /* CRG_STEP_* */
+  int64_t n;               /* elements of x */
+  float* x;                /* [n] the sampler state, in / out */
+  const float* eps;        /* [2][n] the network output of this evaluation */
+  float* x2;               /* [n] HEUN_1 / DPMPP2S_1: out (the second call's input); HEUN_2 / DPMPP2S_2: in (xin) */
+  float* d;                /* [n] HEUN_1: out, HEUN_2: in; LMS: this step's derivative, out */
+  const float* hist[3];    /* LMS: the previous derivatives, newest first; hist[k] read only for k < n_hist */
+  const float* noise;      /* [n] z, read only when add_noise */
+  float c_out;             /* -sigma_q: the evaluation sigma snapped to the denoiser's table */
+  float cfg_scale;
+  float sigma;             /* the divisor of the kind's derivative (> 0 where one is formed) */
+  float dt;
+  float sigma_up, s_noise;
+  float m[4];              /* DPMPP2S_1 / DPMPP2S_2 multipliers (get_mult) */
+  float coef[4];           /* LMS coefficients, newest derivative first */
+  int n_hist;              /* LMS: 0..3 */
+  int one_call;            /* HEUN_1 / DPMPP2S_1: the step makes no second network call */
+  int add_noise;           /* EULER_A, DPMPP2S_1 (one_call), DPMPP2S_2: add (z * s_noise) * sigma_up (next sigma > 0) */
+} crg_sampler_step_args;
+int crg_cfg_sampler_step(crg_ctx* ctx, void* stream, const crg_sampler_step_args* args);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
