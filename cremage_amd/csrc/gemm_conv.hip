@@ -535,15 +535,15 @@ __global__ __launch_bounds__(256 * KG, ((XT != 0 || CRG_LB_A) && KG == 1 && WMT 
   // wave's row l (coalesced: consecutive lanes, consecutive rows of a plane); the values of rows 16 j + frow come over by ds_bpermute.
   // Placed BEHIND the first DMA batches: the fold needs the partials, so the wait it implies covers the DMA latency it runs beside
   // (ahead of them it would put a load round trip in front of every block's first DMA).
-  float ln_a = 0.f, ln_b = 0.f;
+  float ln_r = 0.f, ln_mr = 0.f;
   f32x4 spre[LNE ? WNT : 1];
   if constexpr (LNE) {
     if (kg == 0) {
       const int rl = lane < 16 * WMT ? lane : 16 * WMT - 1;
       const int mr = m0 + wm * (16 * WMT) + rl;
-      const f32x2 ab = ln_fold_row(p.ln_stat, mr < p.M ? mr : p.M - 1, p.ln_parts);
-      ln_a = ab[0];
-      ln_b = ab[1];
+      const f32x2 rm = ln_row_coeffs(p.ln_stat, mr < p.M ? mr : p.M - 1, p.ln_parts, p.K, p.ln_eps);
+      ln_r = rm[0];
+      ln_mr = rm[1];
       const int nb = n0 + wn * (16 * WNT);
 #pragma unroll
       for (int i = 0; i < WNT; ++i) {
@@ -688,15 +688,9 @@ __global__ __launch_bounds__(256 * KG, ((XT != 0 || CRG_LB_A) && KG == 1 && WMT 
   }
   if constexpr (LNE) {
     // y = rstd * (acc - mean * s[n]) (+ bias' in the epilogue): LayerNorm(x) W^T from the GEMM on the raw rows
-    const float invk = 1.0f / (float)p.K;
-    const float mean = ln_a * invk;
-    float var = __builtin_fmaf(-mean, mean, ln_b * invk);
-    var = var > 0.f ? var : 0.f;
-    const float rstd = __builtin_amdgcn_rsqf(var + p.ln_eps);
-    const float mrs = mean * rstd;
 #pragma unroll
     for (int j = 0; j < WMT; ++j) {
-      const float rj = __shfl(rstd, j * 16 + frow), mj = __shfl(mrs, j * 16 + frow);
+      const float rj = __shfl(ln_r, j * 16 + frow), mj = __shfl(ln_mr, j * 16 + frow);
 #pragma unroll
       for (int i = 0; i < WNT; ++i) acc[i][j] = rj * acc[i][j] - mj * spre[i];
     }

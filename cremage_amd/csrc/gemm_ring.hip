@@ -281,14 +281,8 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
     if (LNE && tile_m != ln_tm) {  // (consecutive tiles of a block share their rows in both tile orders: one fetch per block, not per tile)
       ln_tm = tile_m;
       const int mr = m0 + wm * 64 + lane;
-      const f32x2 ab = ln_fold_row(p.ln_stat, mr < p.M ? mr : p.M - 1, p.ln_parts);
-      const float a = ab[0], b = ab[1];
-      const float invk = 1.0f / (float)p.K;
-      const float mean = a * invk;
-      float var = __builtin_fmaf(-mean, mean, b * invk);
-      var = var > 0.f ? var : 0.f;
-      const float rstd = __builtin_amdgcn_rsqf(var + p.ln_eps);
-      const float mrs = mean * rstd;
+      const f32x2 rm = ln_row_coeffs(p.ln_stat, mr < p.M ? mr : p.M - 1, p.ln_parts, p.K, p.ln_eps);
+      const float rstd = rm[0], mrs = rm[1];
 #pragma unroll
       for (int j = 0; j < WMT; ++j) {
         rj[j] = __shfl(rstd, j * 16 + frow);

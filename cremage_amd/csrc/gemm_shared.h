@@ -496,21 +496,32 @@ __device__ __forceinline__ void gemm_epilogue_pairs(const GemmP& p, f32x4 (&acc)
   else body(std::integral_constant<bool, false>{});
 }
 
-// (sum, sum of squares) of one row from its `parts` partials (stat[m][q][2], parts even, <= 16): all the 16-byte loads go out together,
-// clamped duplicates where there are fewer partials (one load latency, not one per partial)
-__device__ __forceinline__ f32x2 ln_fold_row(const float* stat, long m, int parts) {
+// (rstd, mean * rstd) of one row from its `parts` partials (stat[m][q][2] = sum / sum of squares, parts even, <= 16): all the 16-byte
+// loads go out together, clamped duplicates where there are fewer partials (one load latency, not one per partial).
+// var = E[x^2] - mean^2 cancels (mean / sigma)^2-fold.  In fp32 the roundings of the fold, of 1 / K and of mean^2 each cost about
+// 2^-24 (mean / sigma)^2 of the variance: rows with a common offset of 100 sigma come out with rstd off by 5e-4.  bf16's round-off
+// (2e-3) hides that, so the bf16 build keeps the fp32 fold; fp16's (2.4e-4) does not (tests/test_half_type_edges.py: GEGLU rel-L2
+// 9.8e-4 against 2.1e-4 of the output rounding alone), so the fp16 build folds the partials and takes K b - a^2 in fp64 (7.0e-4; what
+// remains is the rounding of the producer's fp32 partials over <= 80 columns).  The same fold in the bf16 build measured + 0.35 % on
+// the SD1.5 step (A/B, five alternating runs each), for an error term that build cannot show.
+#ifdef CRG_F16_BUILD
+typedef double ln_fold_t;
+#else
+typedef float ln_fold_t;
+#endif
+__device__ __forceinline__ f32x2 ln_row_coeffs(const float* stat, long m, int parts, int K, float eps) {
   const f32x4* q = reinterpret_cast<const f32x4*>(stat + m * parts * 2);
   const int nq = parts >> 1;
-  float a = 0.f, b = 0.f;
+  ln_fold_t a = 0, b = 0;
   if (nq <= 4) {
     f32x4 t[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) t[u] = q[u < nq ? u : 0];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float k = u < nq ? 1.f : 0.f;
-      a += k * (t[u][0] + t[u][2]);
-      b += k * (t[u][1] + t[u][3]);
+      const ln_fold_t k = u < nq ? 1 : 0;
+      a += k * ((ln_fold_t)t[u][0] + (ln_fold_t)t[u][2]);
+      b += k * ((ln_fold_t)t[u][1] + (ln_fold_t)t[u][3]);
     }
   } else {
     f32x4 t[8];
@@ -518,12 +529,25 @@ __device__ __forceinline__ f32x2 ln_fold_row(const float* stat, long m, int part
     for (int u = 0; u < 8; ++u) t[u] = q[u < nq ? u : 0];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const float k = u < nq ? 1.f : 0.f;
-      a += k * (t[u][0] + t[u][2]);
-      b += k * (t[u][1] + t[u][3]);
+      const ln_fold_t k = u < nq ? 1 : 0;
+      a += k * ((ln_fold_t)t[u][0] + (ln_fold_t)t[u][2]);
+      b += k * ((ln_fold_t)t[u][1] + (ln_fold_t)t[u][3]);
     }
   }
-  return f32x2{a, b};
+#ifdef CRG_F16_BUILD
+  // var = (K b - a^2) / K^2: the difference in fp64, after which fp32 (and v_rcp_f32's 1 ulp) is enough - no fp64 division
+  const float d = (float)__builtin_fma((double)K, b, -(a * a));
+  const float invk = __builtin_amdgcn_rcpf((float)K);
+  const float rstd = __builtin_amdgcn_rsqf((d > 0.f ? d * invk * invk : 0.f) + eps);
+  return f32x2{rstd, (float)a * invk * rstd};
+#else
+  const float invk = 1.0f / (float)K;
+  const float mean = a * invk;
+  float var = __builtin_fmaf(-mean, mean, b * invk);
+  var = var > 0.f ? var : 0.f;
+  const float rstd = __builtin_amdgcn_rsqf(var + eps);
+  return f32x2{rstd, mean * rstd};
+#endif
 }
 
 template <int N>

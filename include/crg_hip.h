@@ -59,7 +59,11 @@ int crg_version(void);
 /* Which 16-bit element type this build of the library computes in: 0 = bfloat16 (libcrg_hip.so, the default and what
  * BASELINE.json configs[1] names), 1 = IEEE fp16 (libcrg_hip_f16.so: the same kernels with the _f16 matrix instructions - the
  * operand type of the reference's own GPU flow, image_generator.py:489-493,748-751).  In either build `CRG_BF16` in a dtype argument
- * means "the library's half type"; the caller must hand it tensors of that type (cremage_amd.ops does: ops.HALF). */
+ * means "the library's half type"; the caller must hand it tensors of that type (cremage_amd.ops does: ops.HALF).
+ * Range of the fp16 build: half-type operands and results |x| <= 65504.  fp32-class operands (CRG_PREC_BF16X3) are carried as two fp16
+ * planes hi = half(x), lo = half(x - hi): |x| <= 65504 as well, relative resolution 2^-22 for |x| >= 2^-3 and an absolute resolution of
+ * 2^-25 below (lo is an fp16 subnormal there; conversions, LDS-DMA and the _f16 matrix instructions keep subnormals - measured, fp32-class
+ * conv rel-L2 5.7e-7 against fp64, tests/test_half_type_edges.py).  With bf16 planes: fp32's range, relative resolution 2^-16. */
 int crg_half_kind(void);
 int crg_ctx_create(int device, crg_ctx** out);
 void crg_ctx_destroy(crg_ctx* ctx);

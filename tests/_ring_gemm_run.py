@@ -1,5 +1,5 @@
 """Child process of test_linear_ring_gemm (tests/test_hip_ops.py): started with CRG_GEMM_RING=2 CRG_GEMM_RING_MIN=50 so that every
-eligible bf16 GEMM below runs on gemm_ring_kernel; prints ONE JSON line {case: [rel-L2, max-abs, max|ref|, reproducible]}.
+eligible half-type GEMM below runs on gemm_ring_kernel; prints ONE JSON line {case: [rel-L2, max-abs, max|ref|, reproducible]}.
 Not collected by pytest (leading underscore)."""
 import json
 import os
@@ -12,7 +12,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from cremage_amd import ops  # noqa: E402
 
-BF = torch.bfloat16
+BF = ops.HALF  # the library's half type (CRG_HALF is inherited from the parent: bfloat16, or fp16 under tests/test_hip_ops_f16.py)
 
 
 def rnd(*shape, seed=0, scale=1.0):

@@ -6,8 +6,15 @@ Tolerances (stated per dtype):
                      values in fp32, so the remaining error is fp32-accumulate order + one bf16 output
                      rounding: rel-L2 <= 6e-3, max-abs <= 2^-7 * max|ref| (+ small abs floor).
   fp32-class (x3)  : split-bf16 operands carry ~2^-17 relative error each: rel-L2 <= 5e-5.
+
+The half type is the process's (CRG_HALF, as cremage_amd/_lib.py reads it): `BF` below is "the library's 16-bit type", bfloat16 by
+default and IEEE fp16 under CRG_HALF=f16 (tests/test_hip_ops_f16.py runs this file in such a child process against
+libcrg_hip_f16.so).  Every bound that is a statement about half-type round-off is written as <the bf16 figure> * HS, with HS the
+type's unit round-off relative to bf16's (2^-9 -> 1, fp16's 2^-12 -> 1/8).  fp32-class bounds, statistics bounds, bitwise and shape
+assertions do not depend on the half type.
 """
 import math
+import os
 
 import pytest
 import torch
@@ -15,7 +22,9 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
-BF = torch.bfloat16
+HALF_F16 = os.environ.get("CRG_HALF", "bf16").lower() in ("f16", "fp16", "float16", "half")  # cremage_amd/_lib.py:13 (no GPU call here)
+BF = torch.float16 if HALF_F16 else torch.bfloat16  # the library's half type ("bf16" in the names below means this type)
+HS = 2.0 ** -3 if HALF_F16 else 1.0                 # unit round-off of the half type over bf16's: the ONE factor on half-type bounds
 
 
 def _dev():
@@ -28,6 +37,12 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=g) * scale
 
 
+def fig(what, value, bound):
+    """print a measured figure next to its bound (pytest -rP shows it for passing tests too: the headroom tables of the fp16 run)"""
+    print(f"[fig] {what}: {value:.3e} (bound {bound:.3e})")
+    return value
+
+
 def check(got, ref, dtype, what=""):
     got = got.detach().float().cpu()
     ref = ref.detach().float().cpu()
@@ -36,8 +51,10 @@ def check(got, ref, dtype, what=""):
     rel = ((got - ref).norm() / ref.norm().clamp_min(1e-20)).item()
     mx = (got - ref).abs().max().item()
     scale = ref.abs().max().item()
+    fig(what + " rel-L2", rel, 6e-3 * HS if dtype == BF else 5e-5)
+    fig(what + " max-abs", mx, (scale * 2 ** -6 + 1e-3) * HS if dtype == BF else scale * 1e-4 + 1e-5)
     if dtype == BF:
-        assert rel < 6e-3 and mx < scale * 2 ** -6 + 1e-3, (what, rel, mx, scale)
+        assert rel < 6e-3 * HS and mx < (scale * 2 ** -6 + 1e-3) * HS, (what, rel, mx, scale)
     else:
         assert rel < 5e-5 and mx < scale * 1e-4 + 1e-5, (what, rel, mx, scale)
 
@@ -173,7 +190,7 @@ def test_layernorm_as_gemm_epilogue(M, K, N, act, vt, monkeypatch):
         got = torch.cat([qk, vt_[:, :, :T].transpose(1, 2)], dim=-1)
     check(got, ref, BF, f"LN epilogue {M}x{N}x{K} {act}")
     rel = ((got.float().cpu() - ref_plain).norm() / ref_plain.norm()).item()
-    assert rel < 8e-3, rel  # vs fp32 LayerNorm + Linear: bf16 rounding of W o gamma and of the output
+    assert rel < 8e-3 * HS, rel  # vs fp32 LayerNorm + Linear: bf16 rounding of W o gamma and of the output
 
 
 def test_linear_ring_gemm():
@@ -193,7 +210,7 @@ def test_linear_ring_gemm():
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RING_GEMM_RESULT ")][-1][len("RING_GEMM_RESULT "):])
     assert len(res) == 8
     for k, (rel, mx, scale, same) in res.items():
-        assert rel < 6e-3 and mx < scale * 2 ** -6 + 1e-3 and same, (k, rel, mx, scale, same)
+        assert rel < 6e-3 * HS and mx < (scale * 2 ** -6 + 1e-3) * HS and same, (k, rel, mx, scale, same)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -246,7 +263,7 @@ def test_ln_linear(M, N, act, bias):
     two = ops.linear(ops.layer_norm(dx, g.to(_dev()), be.to(_dev()), 1e-5), dw, b.to(_dev()) if bias else None, act=act)
     d = (got.float() - two.float()).abs().max().item()
     # same LN arithmetic up to the order of the fp32 row sums: a few elements of LN(x) may round to the neighbouring bf16
-    assert d <= 2 ** -6 * max(1.0, two.float().abs().max().item()), d
+    assert d <= 2 ** -6 * HS * max(1.0, two.float().abs().max().item()), d
 
 
 @pytest.mark.parametrize("M,N,bias,res", [(4096, 320, True, True), (5000, 320, True, False), (1024, 640, False, True)])
@@ -392,6 +409,7 @@ def test_split_planes_path(C, Co, ks):
                          stride=kw.get("stride", 1), padding=0 if (ks == 1 or kw.get("stride") == 2) else 1)
         if "residual" in kw:
             ref64 = ref64 + res.double().cpu()
+        fig(f"planes conv vs fp64 {sorted(kw)}", (bb.double().cpu() - ref64).abs().max().item(), 3e-5 * max(1.0, ref64.abs().max().item()))
         assert (bb.double().cpu() - ref64).abs().max().item() < 3e-5 * max(1.0, ref64.abs().max().item()), ("vs fp64", kw)
     with pytest.raises(Exception):
         ops.conv2d(hi, w.to(_dev()), bias.to(_dev()), x_lo=lo.float())
@@ -579,7 +597,7 @@ def test_conv_rowhalo_planes(N, C, H, W, Co):
         ref = F.conv2d(x.double(), w.double(), b.double(), padding=1) + (res.double() if with_res else 0.0)
         got = ops.conv2d(hi, w.to(_dev()), b.to(_dev()), x_lo=lo, residual=nhwc(res, torch.float32) if with_res else None)
         assert got.dtype == torch.float32
-        err = (got.double().cpu() - ref).abs().max().item()
+        err = fig("row-halo planes conv vs fp64", (got.double().cpu() - ref).abs().max().item(), 3e-5 * max(1.0, ref.abs().max().item()))
         assert err < 3e-5 * max(1.0, ref.abs().max().item()), (N, C, H, W, Co, with_res, err)
 
 
@@ -607,6 +625,7 @@ def test_conv_planes_gn_stats(N, C, H, W, Co, with_res):
     ref = F.silu(F.group_norm(y.double().cpu(), 32, g.double().cpu(), be.double().cpu(), 1e-6))
     e_pre = ((nh.float() + nl.float()).double().cpu() - ref).abs().max().item()
     e_ref = ((rh.float() + rl.float()).double().cpu() - ref).abs().max().item()
+    fig("GroupNorm planes from conv statistics vs fp64", e_pre, 1e-4)
     assert e_pre < 1e-4 and e_pre < 1.5 * e_ref + 1e-6, (e_pre, e_ref)  # the planes' own resolution (hi + lo: 2^-17 relative) bounds both
     st[0].zero_()                                                              # ... and the side channel really is what was consumed
     zh, _ = ops.group_norm(y, g, be, 32, 1e-6, silu=True, split=True)
@@ -677,9 +696,9 @@ def test_group_norm_golden(dtype, tag):
         ref = g[key]
         err = (got.float().cpu() - ref).abs().max().item()
         # bf16: the input itself is rounded to 8 bits before the statistics (|x| <= ~5 -> 2e-2 of output units after the 1/sigma gain)
-        assert err < (2e-5 if dtype == torch.float32 else 6e-2), (tag, silu, err)
+        assert err < (2e-5 if dtype == torch.float32 else 6e-2 * HS), (tag, silu, err)
         rel = ((got.float().cpu() - ref).norm() / ref.norm()).item()
-        assert rel < (1e-5 if dtype == torch.float32 else 6e-3), (tag, silu, rel)
+        assert rel < (1e-5 if dtype == torch.float32 else 6e-3 * HS), (tag, silu, rel)
 
 
 @pytest.mark.parametrize("N,C1,C2,hw,silu", [(8, 320, 0, 64, True), (8, 640, 0, 32, True), (8, 320, 0, 64, False), (8, 320, 320, 64, True),
@@ -753,7 +772,7 @@ def test_gn_stats_side_channel(case):
     plain = ops.group_norm(y.clone(memory_format=torch.preserve_format), gam, bet, 32, 1e-5, silu=True)  # a clone carries no statistics
     refn = F.silu(F.group_norm(y.float().cpu(), 32, gam.cpu(), bet.cpu(), 1e-5))
     check(fast, refn, BF, case + " gn(pre)")
-    assert (fast.float() - plain.float()).abs().max().item() <= 2 ** -6 * refn.abs().max().item()
+    assert (fast.float() - plain.float()).abs().max().item() <= 2 ** -6 * HS * refn.abs().max().item()
     # written since: the statistics are stale and must not be used
     y.add_(1.0)
     assert ops._gn_stats_of(y, g[2]) is None
@@ -892,8 +911,8 @@ def test_flash_attention(heads, d, Nq, Nk):
     got = ops.attention(qq.to(_dev()).to(BF), kk.to(_dev()).to(BF), vt.to(_dev()).to(BF), heads, Nk, d ** -0.5)
     # P is rounded to bf16 before PV: allow the corresponding extra error
     got, ref = got.float().cpu(), ref
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert torch.isfinite(got).all() and rel < 1e-2, (rel, heads, d, Nq, Nk)
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS)
+    assert torch.isfinite(got).all() and rel < 1e-2 * HS, (rel, heads, d, Nq, Nk)
 
 
 @pytest.mark.parametrize("heads,d,Nq,Nk", [(8, 40, 200, 77), (8, 40, 256, 256), (8, 80, 100, 154), (8, 160, 64, 64), (2, 64, 130, 81),
@@ -916,8 +935,8 @@ def test_flash_attention_row_major_v(heads, d, Nq, Nk, fused):
         kv = torch.cat([dk, dv], dim=-1)
         dk, dv = kv[..., :C], kv[..., C:]
     got = ops.attention_rows_v(dq, dk, dv, heads, d ** -0.5).float().cpu()
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert torch.isfinite(got).all() and rel < 1e-2, (rel, heads, d, Nq, Nk)
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS)
+    assert torch.isfinite(got).all() and rel < 1e-2 * HS, (rel, heads, d, Nq, Nk)
 
 
 def test_flash_attention_row_major_v_spiky_rows():
@@ -930,7 +949,7 @@ def test_flash_attention_row_major_v_spiky_rows():
     kk[0, 70] = qq[0, 9] * 6.0
     ref = attn_ref(q(qq, BF), q(kk, BF), q(vv, BF), heads, d ** -0.5)
     got = ops.attention_rows_v(qq.to(_dev()).to(BF), kk.to(_dev()).to(BF), vv.to(_dev()).to(BF), heads, d ** -0.5).float().cpu()
-    assert ((got - ref).norm() / ref.norm()).item() < 1e-2
+    assert fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS) < 1e-2 * HS
 
 
 @pytest.mark.parametrize("heads,d,Nq,Nk", [(8, 40, 200, 192), (3, 48, 130, 64), (8, 40, 384, 1024), (2, 40, 128, 2048), (4, 64, 256, 256),
@@ -953,8 +972,8 @@ def test_flash_attention_lds_dma_form(heads, d, Nq, Nk):
     dk = wide_k.to(_dev()).to(BF)[..., 8:8 + C]
     vt = vv.transpose(1, 2).contiguous().to(_dev()).to(BF)
     got = ops.attention(dq, dk, vt, heads, Nk, d ** -0.5).float().cpu()
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert torch.isfinite(got).all() and rel < 1e-2, (rel, heads, d, Nq, Nk)
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS)
+    assert torch.isfinite(got).all() and rel < 1e-2 * HS, (rel, heads, d, Nq, Nk)
 
 
 @pytest.mark.parametrize("heads,d,Nq,Nk,row_major_v", [(8, 40, 2100, 77, False), (8, 40, 2100, 77, True), (8, 40, 2048, 4, False), (8, 40, 2048, 4, True),
@@ -988,9 +1007,9 @@ def test_flash_attention_few_keys_kernel(heads, d, Nq, Nk, row_major_v):
         vt[:, :, :Nk] = vv.transpose(1, 2)
         got = ops.attention(dq, kk.to(_dev()).to(BF), vt.to(_dev()).to(BF), heads, Nk, d ** -0.5)
     got = got.float().cpu()
-    rel = ((got - ref).norm() / ref.norm()).item()
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS)
     worst = ((got - ref).flatten(1).norm(dim=1) / ref.flatten(1).norm(dim=1)).max().item()  # per sample: a wrong group cannot hide in the norm
-    assert torch.isfinite(got).all() and rel < 1e-2 and worst < 1.5e-2, (rel, worst, heads, d, Nq, Nk)
+    assert torch.isfinite(got).all() and rel < 1e-2 * HS and worst < 1.5e-2 * HS, (rel, worst, heads, d, Nq, Nk)
 
 
 @pytest.mark.parametrize("gain", [30.0, 300.0])
@@ -1011,8 +1030,8 @@ def test_flash_attention_large_logits(gain):
     assert torch.isfinite(got).all()
     # a near-one-hot softmax amplifies the bf16 rounding of Q * scale * log2(e) (the winner can change between two close keys):
     # compare where the reference softmax is decisive, and bound the rest loosely
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert rel < (2e-2 if gain < 100 else 2e-1), (gain, rel)
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), (2e-2 if gain < 100 else 2e-1) * HS)
+    assert rel < (2e-2 if gain < 100 else 2e-1) * HS, (gain, rel)
 
 
 def test_flash_attention_spiky_rows():
@@ -1027,7 +1046,7 @@ def test_flash_attention_spiky_rows():
     vt = F.pad(vt, (0, (-Nk) % 8))
     ref = attn_ref(q(qq, BF), q(kk, BF), q(vv, BF), heads, d ** -0.5)
     got = ops.attention(qq.to(_dev()).to(BF), kk.to(_dev()).to(BF), vt.to(_dev()).to(BF), heads, Nk, d ** -0.5).float().cpu()
-    assert ((got - ref).norm() / ref.norm()).item() < 1e-2
+    assert fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS) < 1e-2 * HS
 
 
 @pytest.mark.parametrize("dtype,heads,d", [(torch.float32, 4, 32), (torch.float32, 8, 40), (BF, 1, 512), (torch.float32, 1, 512)])
@@ -1038,8 +1057,8 @@ def test_unfused_attention(dtype, heads, d):
     vt = F.pad(vv.transpose(1, 2), (0, (-Nk) % 8)).contiguous()
     ref = attn_ref(q(qq, dtype), q(kk, dtype), q(vv, dtype), heads, d ** -0.5)
     got = ops.attention(qq.to(_dev()).to(dtype), kk.to(_dev()).to(dtype), vt.to(_dev()).to(dtype), heads, Nk, d ** -0.5).float().cpu()
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert rel < (1e-2 if dtype == BF else 5e-5), rel
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS if dtype == BF else 5e-5)
+    assert rel < (1e-2 * HS if dtype == BF else 5e-5), rel
 
 
 @pytest.mark.parametrize("dtype,heads,d", [(BF, 1, 512), (torch.float32, 1, 512), (torch.float32, 4, 32)])
@@ -1055,8 +1074,8 @@ def test_unfused_attention_query_chunks_with_tail(dtype, heads, d, monkeypatch):
     vt = F.pad(vv.transpose(1, 2), (0, (-Nk) % 8)).contiguous()
     ref = attn_ref(q(qq, dtype), q(kk, dtype), q(vv, dtype), heads, d ** -0.5)
     got = ops.attention(qq.to(_dev()).to(dtype), kk.to(_dev()).to(dtype), vt.to(_dev()).to(dtype), heads, Nk, d ** -0.5).float().cpu()
-    rel = ((got - ref).norm() / ref.norm()).item()
-    assert rel < (1e-2 if dtype == BF else 5e-5), rel
+    rel = fig("attention rel-L2", ((got - ref).norm() / ref.norm()).item(), 1e-2 * HS if dtype == BF else 5e-5)
+    assert rel < (1e-2 * HS if dtype == BF else 5e-5), rel
 
 
 # ------------------------------------------------------------------------------------------ small ops
