@@ -17,7 +17,7 @@ BF16, F32, F16 = 0, 1, 2
 PREC_BF16, PREC_BF16X3, PREC_F16MX = 0, 1, 2
 EPI_NONE, EPI_SILU, EPI_GEGLU = 0, 1, 2
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
-PACK_LINEAR, PACK_CONV, PACK_GEGLU = 0, 1, 2
+PACK_LINEAR, PACK_CONV, PACK_GEGLU, PACK_CONV_UP2 = 0, 1, 2, 3
 K_SLOTS = 17  # enum crg_kernel_slot
 SLOT_NAMES = ["gemm_w1", "gemm_w4", "gemm_w5", "gemm_x3", "conv_w1", "conv_w4", "conv_w5", "conv_x3", "splitk_reduce", "attention",
               "gn_stats", "gn_apply", "layernorm", "elementwise", "conv_small", "softmax", "lngemm"]

@@ -173,6 +173,30 @@ __global__ void pack_kernel(const ST* __restrict__ src, bf16* __restrict__ hi, b
   }
 }
 
+// CRG_PACK_CONV_UP2: [Cout][Cin][3][3] -> the parity image [parity a b][Cout][Cin / 64][u][v][64] of the conv behind a nearest-2x upsample
+// (conv3_rowhalo_kernel<.., TAPS = 2>): W'_ab[u][v] = sum of W[kh][kw] over kh in rows(a, u), kw in rows(b, v), rows(0, .) = {0}, {1, 2},
+// rows(1, .) = {0, 1}, {2} - the taps that read the same source pixel.  Summed in fp32 in a fixed order, THEN rounded once (or split hi / lo).
+template <typename ST>
+__global__ void pack_up2_kernel(const ST* __restrict__ src, bf16* __restrict__ hi, bf16* __restrict__ lo, int n_out, int n_in, long total) {
+  for (long d = (long)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += (long)gridDim.x * blockDim.x) {
+    const int kk = 4 * n_in;
+    const long row = d / kk;
+    const int k = (int)(d - row * kk);
+    const int par = (int)(row / n_out), o = (int)(row - (long)par * n_out);
+    const int chunk = k >> 8, u = (k >> 7) & 1, v = (k >> 6) & 1, ci = chunk * 64 + (k & 63);
+    const int a = par >> 1, b = par & 1;
+    const int kh0 = u ? 1 + a : 0, kh1 = u ? 2 : a;  // (a, u): (0,0) -> 0..0, (0,1) -> 1..2, (1,0) -> 0..1, (1,1) -> 2..2
+    const int kw0 = v ? 1 + b : 0, kw1 = v ? 2 : b;
+    const ST* w = src + ((long)o * n_in + ci) * 9;
+    float f = 0.f;
+    for (int kh = kh0; kh <= kh1; ++kh)
+      for (int kw = kw0; kw <= kw1; ++kw) f += (float)w[kh * 3 + kw];
+    const bf16 h = (bf16)f;
+    hi[d] = h;
+    if (lo) lo[d] = (bf16)(f - (float)h);
+  }
+}
+
 __global__ void pack_geglu_bias_kernel(const float* __restrict__ src, float* __restrict__ dst, int n2) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= n2) return;
@@ -276,6 +300,18 @@ extern "C" int crg_pack_weight(crg_ctx* ctx, void* stream, const void* src, int 
                                int ksize, void* dst_hi, void* dst_lo) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, src && dst_hi && n_out > 0 && n_in > 0, "pack_weight: bad arguments");
+  if (kind == CRG_PACK_CONV_UP2) {
+    CRG_REQUIRE(ctx, ksize == 3 && n_in % 64 == 0, "pack_weight: the parity image takes 3x3 weights with Cin %% 64 == 0 (ksize %d, Cin %d)", ksize, n_in);
+    const long total = 16L * n_out * n_in;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == CRG_F32) hipLaunchKernelGGL(pack_up2_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else if (src_dtype == CRG_BF16) hipLaunchKernelGGL(pack_up2_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else if (src_dtype == CRG_F16) hipLaunchKernelGGL(pack_up2_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else return crg_fail(ctx, -22, "pack_weight: unsupported source dtype %d", src_dtype);
+    CRG_CHECK_LAUNCH(ctx, "pack_weight");
+    return 0;
+  }
   if (kind != CRG_PACK_CONV) ksize = 1;
   CRG_REQUIRE(ctx, ksize == 1 || ksize == 3, "pack_weight: ksize %d unsupported", ksize);
   if (kind == CRG_PACK_GEGLU) CRG_REQUIRE(ctx, n_out % 32 == 0, "pack_weight: GEGLU needs n_out %% 32 == 0, got %d", n_out);

@@ -778,8 +778,18 @@ __global__ __launch_bounds__(256 * KG, ((XT != 0 || CRG_LB_A) && KG == 1 && WMT 
 // instructions per k-tile and wave then cost 7.7 ms where their bare issue time (33.5 cycles each beside 16 x 18 for the main pass) predicts
 // about 3: in this loop the block-scaled instruction is about twice as expensive as in a bare loop.  Next: e2m3 cross operands (19.5
 // cycles per instruction) and 32 x 32 x 64 tiles.
-template <int WNT, typename YT, bool PAIR, int NS = 1, int KG = 1, int MT = 1, bool MX = false>
+// TAPS = 2 (p.up == 2): the conv behind a nearest-2x upsample as four 2x2 convs ON THE SOURCE GRID, one per output parity (a, b):
+//   y[2i + a][2j + b] = sum_{u, v in {0, 1}} W'_ab[u][v] x[i + a - 1 + u][j + b - 1 + v]
+// with W'_ab the sums of the 3x3 taps that read the same source pixel (crg_pack_weight CRG_PACK_CONV_UP2: [parity][Cout][Cin / 64][u][v][64],
+// ldw = 4 Cin) - 4 / 9 of the multiplies of the gather form above.  The GEMM rows are VIRTUAL: mv = ((img * 4 + parity) * H + i) * W + j, i.e.
+// a batch of 4 N source-sized images, so the row buffers are exactly those of a plain conv on H x W; a tile never straddles a parity
+// (H W % TP == 0, host-checked), which makes the parity block-uniform.  A group is (chunk, kernel row kh = a + u): its TWO k-tiles read the
+// row buffer at pixel offsets b and b + 1, and the next group's pieces are spread over two k-tiles instead of three (every k-tile still
+// starts with vmcnt(0) + barrier: same hazard argument).  Only the output address differs in the epilogue (up2_out_row); split-K slabs and
+// the GroupNorm statistics stay in mv order, which is per-sample contiguous.  rows / seg geometries only.
+template <int WNT, typename YT, bool PAIR, int NS = 1, int KG = 1, int MT = 1, bool MX = false, int TAPS = 3>
 __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void conv3_rowhalo_kernel(GemmP p) {
+  static_assert(TAPS == 3 || (TAPS == 2 && !MX), "TAPS: 3, or 2 for the sub-pixel form of the upsample conv (not on the MX arm)");
   static_assert(!PAIR || (sizeof(YT) == 2 && NS == 1), "paired columns: bf16 output, single-plane operands");
   static_assert(MT == 1 || (KG == 1 && NS == 1), "256-row tiles: single-plane operands, no in-block split-K");
   static_assert(!MX || (NS == 2 && KG == 2 && MT == 1), "MX: the split-plane form on two k-groups");
@@ -800,11 +810,12 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
   const int kg = MT == 2 ? 0 : wave >> 2;
   const int wm = MT == 2 ? wave >> 1 : (wave & 3) >> 1, wn = wave & 1;
   // geometry lives on the OUTPUT grid (Ho x Wo; the nearest-2x upsampled image when p.up), sources are read at (h >> up, w >> up)
-  const int Wd = p.Wo, Hd = p.Ho, sh = p.up ? 1 : 0;
+  // (TAPS == 2: the geometry is the SOURCE grid, images = (sample, parity) pairs)
+  const int Wd = TAPS == 2 ? p.W : p.Wo, Hd = TAPS == 2 ? p.H : p.Ho, sh = (TAPS == 3 && p.up) ? 1 : 0;
   // three buffer geometries: rows (W divides the tile: R whole image rows, each with a zero / neighbour pixel left and right),
   // seg (W a multiple of the tile: one row segment) and lin (any other width: the TP + 2 pixels m0 - 1 .. m0 + TP in linear
   // pixel order; a tap that would wrap around an image row is zeroed in the A fragment instead of in the buffer)
-  const bool lin = p.halo_lin != 0;
+  const bool lin = TAPS == 3 && p.halo_lin != 0;
   const bool seg = lin || Wd > TP;       // lin shares seg's addressing: buffer pixel b <-> linear pixel m0 - 1 + b
   const int WP = seg ? TP + 2 : Wd + 2;
   const int R = seg ? 1 : TP / Wd;
@@ -818,7 +829,9 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
   block_to_tile(p, tile_m, tile_n, sid);
   const int m0 = tile_m * TP, n0 = tile_n * BN;
   const int bz = 0;
-  const bf16* Wp = p.w;
+  const int par = TAPS == 2 ? (m0 / (Hd * Wd)) & 3 : 0;  // output parity (a, b) = (par >> 1, par & 1) of this tile
+  const int par_a = par >> 1, par_b = par & 1;
+  const bf16* Wp = p.w + (long)par * p.N * p.ldw;         // its slab of the parity weight image
   const long a_lo_off = NS == 2 ? reinterpret_cast<const bf16*>(p.a_lo) - reinterpret_cast<const bf16*>(p.a) : 0;
   const long w_lo_off = NS == 2 ? p.w_lo - p.w : 0;
   const bf16* zpage = p.zero_page;
@@ -854,7 +867,7 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
       if (ok) msk = (h >= 1 ? 1u : 0u) | 2u | (h + 1 < Hd ? 4u : 0u);
       xmask[i] = msk;
       xh[i] = h;
-      xsrc[i] = img * p.H * p.W + (w >> sh);
+      xsrc[i] = (TAPS == 2 ? img >> 2 : img) * p.H * p.W + (w >> sh);
     }
   }
   bool wok[WL];
@@ -866,12 +879,12 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
     wok[q] = n < p.N && (wave + NW * q) < WRG;
     wrow_off[q] = (long)n * p.ldw;
   }
-  // K slice of this block in (chunk, kernel row) groups of three k-tiles (ks_q / ks_r are in groups for this kernel)
+  // K slice of this block in (chunk, kernel row) groups of TAPS k-tiles (ks_q / ks_r are in groups for this kernel)
   const int g_begin = sid * p.ks_q + (sid < p.ks_r ? sid : p.ks_r);
   const int g_end = g_begin + p.ks_q + (sid < p.ks_r ? 1 : 0);
 
-  auto stage_x = [&](int g, int slot) {  // this wave's pieces i with i % 3 == slot of group g's row buffer(s)
-    const int c = g / 3, kh = g - 3 * c;
+  auto stage_x = [&](int g, int slot) {  // this wave's pieces i with i % TAPS == slot of group g's row buffer(s)
+    const int c = g / TAPS, kh = g - TAPS * c + par_a;
     const int cch = c * 64 + clog * 8;
     const bool second = cch >= p.C1;
     const bf16* base = reinterpret_cast<const bf16*>(second ? p.x2 : p.a);
@@ -880,7 +893,7 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
     char* xb = xbuf + ((g - g_begin) & 1) * (NS * xbuf_bytes);
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
-      if (i % 3 != slot) continue;
+      if (i % TAPS != slot) continue;
       const int jp = wave + NW * i;
       if (jp < XP) {  // wave-uniform
         const bool ok = (xmask[i] >> kh) & 1u;
@@ -983,8 +996,8 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
   if (g_begin < g_end) {
     stage_x(g_begin, 0);
     stage_x(g_begin, 1);
-    stage_x(g_begin, 2);
-    stage_w(3 * g_begin, 0);
+    if constexpr (TAPS == 3) stage_x(g_begin, 2);
+    stage_w(TAPS * g_begin, 0);
   }
   // KG == 2: the two k-groups are the two waves of every SIMD (wave w and w + 4).  Run in lockstep they read their fragments together
   // and multiply together, and the matrix pipe idles during the reads.  The second group therefore runs its MFMAs ONE K-TILE LATE, from
@@ -1080,14 +1093,15 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
   for (int g = g_begin; g < g_end; ++g) {
     const char* xs = xbuf + ((g - g_begin) & 1) * (NS * xbuf_bytes);
 #pragma unroll
-    for (int kw = 0; kw < 3; ++kw) {
+    for (int kt = 0; kt < TAPS; ++kt) {
+      const int kw = TAPS == 2 ? kt + par_b : kt;  // buffer pixel offset of this k-tile's tap
       wait_vmcnt<0>();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       __builtin_amdgcn_s_setprio(2);
-      if (kw < 2 || g + 1 < g_end) stage_w(3 * g + kw + 1, wbuf ^ 1);
-      if (g + 1 < g_end) stage_x(g + 1, kw);
+      if (kt < TAPS - 1 || g + 1 < g_end) stage_w(TAPS * g + kt + 1, wbuf ^ 1);
+      if (g + 1 < g_end) stage_x(g + 1, kt);
       __builtin_amdgcn_s_setprio(0);
       const char* ws = wring + wbuf * (NS * WS_BYTES);
       if constexpr (STAG) {
@@ -1202,9 +1216,9 @@ __global__ __launch_bounds__(256 * KG * MT, (KG == 1 && MT == 1) ? 2 : 1) void c
       for (int j = 0; j < WMT; ++j) acc[i][j] += red[(i * WMT + j) * 64];
   }
   if constexpr (PAIR) {
-    gemm_epilogue_pairs<WNT, WMT>(p, acc, m0, n0, wm, wn, frow, fq, bz, r2, r1, pre_res, bpre, pre_bias);
+    gemm_epilogue_pairs<WNT, WMT, 2, false, TAPS == 2>(p, acc, m0, n0, wm, wn, frow, fq, bz, r2, r1, pre_res, bpre, pre_bias);
   } else {
-    gemm_epilogue<WNT, YT, WMT>(p, acc, m0, n0, wm, wn, frow, fq, bz, sid, rres, pre_res, bpre, pre_bias);
+    gemm_epilogue<WNT, YT, WMT, TAPS == 2>(p, acc, m0, n0, wm, wn, frow, fq, bz, sid, rres, pre_res, bpre, pre_bias);
   }
 }
 
@@ -1236,7 +1250,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmP p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] += (float)rp[e];
     }
-    YT* yp = Y + (long)m * p.ldy + n;
+    YT* yp = Y + (p.up == 2 ? up2_out_row(p, m) : (long)m) * p.ldy + n;
     if ((p.ldy & 3) == 0) {
       if constexpr (sizeof(YT) == 2) {
         bf16x4 o4;
@@ -1302,7 +1316,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(GemmP p) {
         s1[e] += f;
         s2[e] += f * f;
       }
-      YT* yp = Y + (long)m * p.ldy + n;
+      YT* yp = Y + (p.up == 2 ? up2_out_row(p, m) : (long)m) * p.ldy + n;
       if constexpr (sizeof(YT) == 2) *reinterpret_cast<uint2*>(yp) = *reinterpret_cast<const uint2*>(o);
       else *reinterpret_cast<f32x4*>(yp) = *reinterpret_cast<const f32x4*>(o);
     }
@@ -1629,22 +1643,27 @@ int launch_kernel(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   int threads = GLDS ? 256 * KG : 256 * NSPLIT;
   if constexpr (GLDS && CONV && STAGES == 2 && WMT == 4 && KG == 1 && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 2;  // dev knob: 0 = plain implicit GEMM
-    const int ngroups = (p.K / BK) / 3;
-    if (knob && p.rowhalo && batch == 1 && p.splits <= ngroups) {
+    const bool up2 = p.up == 2;  // sub-pixel form: groups of two k-tiles, geometry of the source grid, this kernel only (no knob)
+    const int ngroups = (p.K / BK) / (up2 ? 2 : 3);
+    if ((knob || up2) && p.rowhalo && batch == 1 && p.splits <= ngroups) {
       halo = true;
       const int TP = p.rowhalo == 2 ? 256 : 128;
       if (p.rowhalo == 2) {
-        kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 2>;
+        if (up2) kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 2, false, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 2, false, 2>;
+        else kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 2>;
         threads = 512;
       } else {
-        kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true> : conv3_rowhalo_kernel<WNT, YT, false>;
+        if (up2) kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 1, false, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 1, false, 2>;
+        else kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true> : conv3_rowhalo_kernel<WNT, YT, false>;
       }
-      const int XP = (p.halo_lin || p.Wo > TP) ? (TP + 2 + 7) / 8 : ((TP / p.Wo) * (p.Wo + 2) + 7) / 8;
+      const int Wg = up2 ? p.W : p.Wo;
+      const int XP = (p.halo_lin || Wg > TP) ? (TP + 2 + 7) / 8 : ((TP / Wg) * (Wg + 2) + 7) / 8;
       lds_bytes = (size_t)2 * BN * 128 + (size_t)2 * XP * 1024;
       p.ks_q = ngroups / p.splits;  // K slices in (chunk, kernel row) groups
       p.ks_r = ngroups % p.splits;
     }
   }
+  if (p.up == 2 && !halo) return crg_fail(ctx, -22, "conv2d: the sub-pixel upsample form runs on the row-halo kernel only (Cout > 32, bf16 output or split planes)");
   {
     const size_t cap = halo ? (size_t)(p.rowhalo == 2 ? 116 : 80) * 1024 : lds;
     if (int rc = crg_set_dyn_lds(ctx, reinterpret_cast<const void*>(kern), cap, "gemm")) return rc;
@@ -1704,6 +1723,7 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     else if (blocks < (CONV ? (p.ks == 1 ? d_max_c1 : d_max_g) : (p.epi == CRG_EPI_GEGLU ? d_max_g : d_max))) cfg = 4;
   }
   if (GLDS && force) cfg = force;
+  if (p.up == 2) cfg = 1;  // the sub-pixel upsample form exists on the row-halo kernel (configuration A's place) only
   if (cfg == 3 || cfg == 4) {
     p.tiles_m = (p.M + 63) / 64;
     p.splits = force ? choose_splits(p, p.tiles_n * p.tiles_m, batch) : 1;
@@ -1711,9 +1731,10 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     // row-halo conv on 256-row tiles (one 8-wave block per CU): same K slices, half the m-tiles
     static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 2;  // dev knob: 0 plain implicit GEMM, 1 128-row tiles only
-    const int ngroups = (p.K / BK) / 3;
+    const int ngroups = (p.K / BK) / (p.up == 2 ? 2 : 3);
+    const int Wg = p.up == 2 ? p.W : p.Wo;  // (sub-pixel form: source-grid geometry, tiles must not straddle a parity)
     if (knob == 2 && cfg == 1 && p.rowhalo && batch == 1 && p.splits <= ngroups && p.M % 256 == 0 &&
-        (p.halo_lin || (p.Wo <= 256 ? 256 % p.Wo == 0 : p.Wo % 256 == 0))) {
+        (p.halo_lin || (Wg <= 256 ? 256 % Wg == 0 : Wg % 256 == 0)) && (p.up != 2 || (p.H * p.W) % 256 == 0)) {
       // one block per CU: only when the grid fills its rounds of 256 blocks (a 288-block grid would run a second round 1/8 full)
       const long blocks2 = (long)(p.M / 256) * p.tiles_n * p.splits;
       const long rounds = (blocks2 + 255) / 256;
@@ -1726,7 +1747,7 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   p.ring = 0;
   if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     // the staggered-wave kernel (conv_pp.hip) for the 256-row configuration, where its buffer descriptors can address the operands
-    if (p.rowhalo == 2 && p.a_bytes && p.w_bytes && (p.C2 == 0 || p.x2_bytes) && (long)p.M / (p.Ho * p.Wo) * p.H * p.W < (1 << 24)) p.ring = 1;
+    if (p.rowhalo == 2 && p.up != 2 && p.a_bytes && p.w_bytes && (p.C2 == 0 || p.x2_bytes) && (long)p.M / (p.Ho * p.Wo) * p.H * p.W < (1 << 24)) p.ring = 1;
   }
   if (p.splits > 1) {
     const size_t bytes = (size_t)batch * p.splits * p.M * p.N * sizeof(float);
@@ -1809,11 +1830,14 @@ int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   bool halo = false;
   if constexpr (CONV && (WNT == 4 || WNT == 5)) {
     static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 1;  // dev knob: 0 = plain implicit GEMM
-    const int ngroups = (p.K / BK) / 3;
-    if (knob && p.rowhalo && batch == 1 && p.splits <= ngroups) {
+    const bool up2 = p.up == 2;  // sub-pixel form: groups of two k-tiles, geometry of the source grid, this kernel only (no knob)
+    const int ngroups = (p.K / BK) / (up2 ? 2 : 3);
+    if ((knob || up2) && p.rowhalo && batch == 1 && p.splits <= ngroups) {
       halo = true;
-      kern = p.mx ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, true> : conv3_rowhalo_kernel<WNT, float, false, 2, 2>;
-      const int XP = (p.halo_lin || p.Wo > 128) ? 17 : ((128 / p.Wo) * (p.Wo + 2) + 7) / 8;
+      kern = p.mx ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, true>
+                  : up2 ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, false, 2> : conv3_rowhalo_kernel<WNT, float, false, 2, 2>;
+      const int Wg = up2 ? p.W : p.Wo;
+      const int XP = (p.halo_lin || Wg > 128) ? 17 : ((128 / Wg) * (Wg + 2) + 7) / 8;
       lds_bytes = (size_t)2 * 2 * BN * 128 + (size_t)2 * 2 * XP * 1024;
       units = ngroups;  // ... or in (chunk, kernel row) groups
     }
@@ -1822,6 +1846,7 @@ int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     const size_t cap = halo ? (size_t)(2 * 2 * BN * 128 + 2 * 2 * 18 * 1024) : lds;  // eligible widths need <= 18 pieces per row buffer
     if (int rc = crg_set_dyn_lds(ctx, reinterpret_cast<const void*>(kern), cap, "gemm(planes)")) return rc;
   }
+  if (p.up == 2 && !halo) return crg_fail(ctx, -22, "conv2d: the sub-pixel upsample form runs on the row-halo kernel only (Cout > 32)");
   if (p.mx && !halo) return crg_fail(ctx, -22, "conv2d: the MX form takes 3x3 / stride 1 / pad 1 convs with Cin %% 64 == 0 (the row-halo kernel's domain)");
   {
     p.ks_q = units / p.splits;
@@ -1950,7 +1975,21 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   CRG_REQUIRE(ctx, a->Cout % 4 == 0 || !a->cvec, "conv2d: a per-sample channel vector needs Cout %% 4 == 0 (got %d)", a->Cout);
   CRG_REQUIRE(ctx, ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->w & 15) == 0 && ((uintptr_t)a->bias & 15) == 0 && ((uintptr_t)a->cvec & 15) == 0,
               "conv2d: pointers must be 16-byte aligned");
+  CRG_REQUIRE(ctx, a->upsample2x >= 0 && a->upsample2x <= 2, "conv2d: upsample2x = %d (0 none, 1 folded into the gather, 2 sub-pixel form)", a->upsample2x);
+  const bool up2 = a->upsample2x == 2;
   const int Hv = a->upsample2x ? 2 * a->H : a->H, Wv = a->upsample2x ? 2 * a->W : a->W;
+  if (up2) {
+    // w / w_lo are the parity image of CRG_PACK_CONV_UP2; conv3_rowhalo_kernel<.., TAPS = 2> on 128-row tiles of the source grid at least
+    CRG_REQUIRE(ctx, a->ksize == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 && a->Ho == Hv && a->Wo == Wv,
+                "conv2d: the sub-pixel upsample form is a 3x3 / stride 1 / pad 1 conv of the upsampled image");
+    CRG_REQUIRE(ctx, Ctot % 64 == 0 && a->Cout > 32, "conv2d: the sub-pixel upsample form needs Cin %% 64 == 0 and Cout > 32 (got %d, %d)", Ctot, a->Cout);
+    CRG_REQUIRE(ctx, !a->x2 && !a->cvec && !a->residual && !a->gn_y, "conv2d: the sub-pixel upsample form takes no second input, channel vector, residual or fused GroupNorm");
+    CRG_REQUIRE(ctx, a->x_dtype == CRG_BF16 && ((a->prec == CRG_PREC_BF16 && a->y_dtype == CRG_BF16 && !a->x_lo) ||
+                                                (a->prec == CRG_PREC_BF16X3 && a->y_dtype == CRG_F32 && a->x_lo && a->w_lo)),
+                "conv2d: the sub-pixel upsample form takes a 16-bit x plane: bf16 in / out, or BF16X3 on pre-split planes with fp32 output");
+    CRG_REQUIRE(ctx, (a->H * a->W) % 128 == 0 && a->W >= 16 && (a->W <= 128 ? 128 % a->W == 0 : a->W % 128 == 0),
+                "conv2d: the sub-pixel upsample form needs H * W %% 128 == 0 and a source width of 16..128 that divides 128, or a multiple of 128 (got %dx%d)", a->H, a->W);
+  }
   CRG_REQUIRE(ctx, a->Ho > 0 && a->Wo > 0 && (a->Ho - 1) * a->stride - a->pad_t < Hv && (a->Wo - 1) * a->stride - a->pad_l < Wv,
               "conv2d: output %dx%d inconsistent with input %dx%d stride %d", a->Ho, a->Wo, Hv, Wv, a->stride);
   if (a->x_lo) {
@@ -1975,6 +2014,7 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   p.cvec = a->cvec; p.cvec_rows = a->Ho * a->Wo; p.cvec_ld = a->cvec_ld ? a->cvec_ld : a->Cout;
   p.H = a->H; p.W = a->W; p.Ho = a->Ho; p.Wo = a->Wo; p.ks = a->ksize; p.stride = a->stride;
   p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.up = a->upsample2x;
+  if (up2) p.ldw = p.K = 4 * Ctot;  // per parity: 2 x 2 taps; the four [Cout][4 Cin] slabs follow each other
   if (a->prec == CRG_PREC_F16MX) {
     // mx_log2 = {w hi8, w lo8, x hi8, x lo8}: each plane stores value * 2^s, the instruction's E8M0 scale undoes it (127 - s).
     // k-group 0 multiplies w lo8 by x hi8, k-group 1 w hi8 by x lo8.
@@ -1992,6 +2032,7 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
                ((a->y_dtype == CRG_BF16 && a->prec == CRG_PREC_BF16) || (a->y_dtype == CRG_F32 && (a->prec == CRG_PREC_BF16X3 || a->prec == CRG_PREC_F16MX) && a->x_lo)))
                   ? 1 : 0;
   p.halo_lin = (a->Wo >= 16 && (a->Wo <= 128 ? 128 % a->Wo == 0 : a->Wo % 128 == 0)) ? 0 : 1;  // geometry of the output grid
+  if (up2) p.halo_lin = 0;  // (geometry of the source grid: checked above)
   {
     const double ab = (double)a->N * a->H * a->W * a->C1 * 2.0, xb = (double)a->N * a->H * a->W * a->C2 * 2.0, wb = (double)p.N * p.K * 2.0;
     const double lim = 2147483648.0;
@@ -2006,12 +2047,13 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
     p.gn_gamma = a->gn_gamma; p.gn_beta = a->gn_beta; p.gn_eps = a->gn_eps; p.gn_groups = a->gn_groups; p.gn_silu = a->gn_silu;
     p.gn_hw = a->Ho * a->Wo; p.gn_y = a->gn_y;
   }
+  const double wbytes = (double)p.N * p.K * 2 * (up2 ? 4 : 1);  // (sub-pixel form: four parity slabs; K = 4 Cin, so `flops` is the executed work)
   const double flops = 2.0 * p.M * (double)p.N * p.K;
-  const double bytes = (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype) + (double)p.N * p.K * 2 +
+  const double bytes = (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype) + wbytes +
                        (double)p.M * p.N * crg_dtype_size(a->y_dtype) * (a->residual ? 2 : 1);
   ctx->gn_fused = false;
   const int rc = dispatch<true>(ctx, (hipStream_t)stream, p, 1, a->x_dtype, a->y_dtype, a->prec,
-                                Work{flops, bytes, (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype), (double)p.N * p.K * 2});
+                                Work{flops, bytes, (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype), wbytes});
   if (a->gn_stats_rows) *a->gn_stats_rows = p.gstat_rows;
   if (rc || !a->gn_y || ctx->gn_fused) return rc;
   // not split along K (or a shape the fused kernel does not take): the GroupNorm runs as its own launch(es) on the finished y

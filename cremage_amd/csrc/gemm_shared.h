@@ -108,11 +108,22 @@ __device__ __forceinline__ float row16_sum(float v) {
   return v;
 }
 
+// Sub-pixel form of the upsample conv (p.up == 2, conv3_rowhalo_kernel<.., TAPS = 2>): GEMM row mv = ((img * 4 + parity) * H + i) * W + j
+// of the virtual (sample, parity) batch on the source grid -> row of y (the 2 H x 2 W image) it is stored at.  Everything else - split-K
+// slabs, the GroupNorm statistics blocks - stays in mv order.
+__device__ __forceinline__ long up2_out_row(const GemmP& p, int mv) {
+  const int hw = p.H * p.W;
+  const int vimg = mv / hw, rem = mv - vimg * hw;
+  const int i = rem / p.W, j = rem - i * p.W;
+  return ((long)(vimg >> 2) * p.Ho + 2 * i + ((vimg >> 1) & 1)) * p.Wo + 2 * j + (vimg & 1);
+}
+
 // ---- shared epilogue: lane holds rows n = ..+fq*4+{0..3}, column m = ..+frow of each 16x16 tile ----
 // fp32 outputs with p.gstat set (the fp32-class VAE convs, round 3): per 32-row block and channel the sum and the sum of squares of the
 // stored values go to the statistics side channel (planes as in the bf16 path), so that the GroupNorm behind the conv
 // (model.py:99-113 -> :116-121 of the next ResnetBlock) does not read the fp32 tensor - up to 1 GB - once more for them.
-template <int WNT, typename YT, int WMT = 4>
+// UP2: the finished rows go to up2_out_row(m) of y (no residual / cvec in that form: host-checked)
+template <int WNT, typename YT, int WMT = 4, bool UP2 = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[WNT][WMT], int m0, int n0, int wm, int wn, int frow, int fq,
                                               int bz, int sid, const bf16x4 (&pre)[WNT][WMT], bool use_pre,
                                               const f32x4 (&bpre)[WNT], bool use_bpre) {
@@ -211,7 +222,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[WNT][
           for (int e = 0; e < 4; ++e) v[e] = crg_silu_f(v[e]);
         }
         if (cv) v += *reinterpret_cast<const f32x4*>(cv + n);
-        const long yo = (long)m * p.ldy + n;
+        const long yo = (UP2 ? up2_out_row(p, m) : (long)m) * p.ldy + n;
         if (use_pre) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] += (float)pre[i][j][e];
@@ -257,7 +268,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmP& p, f32x4 (&acc)[WNT][
           if (p.epi == CRG_EPI_SILU) s = crg_silu_f(s);
           if (cv) s += cv[n + e];
           if (R) s += (float)R[(long)m * p.ldr + n + e];
-          Y[(long)m * p.ldy + n + e] = (YT)s;
+          Y[(UP2 ? up2_out_row(p, m) : (long)m) * p.ldy + n + e] = (YT)s;
         }
       }
     }
@@ -298,7 +309,7 @@ __device__ __forceinline__ int unpair_col(int pos) {  // LDS row position within
 // tile_lds (block-uniform; needs p.gstat): TILE statistics - the wave sums over ALL its rows and leaves its per-column sums in LDS
 // (tile_lds[wave slot][2][16 WNT], wave slot = wm * 2 + wn) behind a block barrier (every wave is past its K loop: the LDS is free);
 // the calling kernel folds the row waves and writes one partial per tile and column (p.gstat_rows = tile height).
-template <int WNT, int WMT, int SM = 2, bool RS = false>
+template <int WNT, int WMT, int SM = 2, bool RS = false, bool UP2 = false>
 __device__ __forceinline__ void gemm_epilogue_pairs(const GemmP& p, f32x4 (&acc)[WNT][WMT], int m0, int n0, int wm, int wn, int frow,
                                                     int fq, int bz, const bf16x8 (&r2)[WNT / 2 > 0 ? WNT / 2 : 1][WMT],
                                                     const bf16x4 (&r1)[WMT], bool has_res, const f32x4 (&bpre)[WNT], bool has_bias,
@@ -316,6 +327,7 @@ __device__ __forceinline__ void gemm_epilogue_pairs(const GemmP& p, f32x4 (&acc)
     for (int j = 0; j < WMT; ++j) {
       const int m = m0 + wm * (16 * WMT) + j * 16 + frow;
       const bool valid = m < p.M;
+      const long my = UP2 ? up2_out_row(p, valid ? m : 0) : (long)m;  // row of y
       if constexpr (!STATS) {
         if (!valid) continue;
       } else if ((j & 1) == 0 && (tile_lds == nullptr || j == 0)) {
@@ -357,7 +369,7 @@ __device__ __forceinline__ void gemm_epilogue_pairs(const GemmP& p, f32x4 (&acc)
           o[e] = (bf16)a[e];
           o[4 + e] = (bf16)b[e];
         }
-        if (valid) *reinterpret_cast<bf16x8*>(Y + (long)m * p.ldy + n) = o;
+        if (valid) *reinterpret_cast<bf16x8*>(Y + my * p.ldy + n) = o;
         if constexpr (RS) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
@@ -386,7 +398,7 @@ __device__ __forceinline__ void gemm_epilogue_pairs(const GemmP& p, f32x4 (&acc)
           bf16x4 o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16)a[e];
-          if (valid) *reinterpret_cast<bf16x4*>(Y + (long)m * p.ldy + n) = o;
+          if (valid) *reinterpret_cast<bf16x4*>(Y + my * p.ldy + n) = o;
           if constexpr (RS) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

@@ -69,6 +69,9 @@ class Upsample(nn.Module):
 
     def forward(self, x):
         assert x.shape[1] == self.channels
+        # gather form (ops.conv2d's default for 16-bit operands), not the sub-pixel one: its pre-summed taps are rounded to the operand
+        # type once more (2e-3 of one conv's output), and 20 sampler steps grow that to 3.5e-2 of the final latents (DESIGN.md section 6,
+        # round 5)
         return self.conv(x, upsample2x=True, gn_stats=True)  # feeds the next ResBlock's GroupNorm
 
 

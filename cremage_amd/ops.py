@@ -283,14 +283,17 @@ def packed_weight(w: torch.Tensor, kind: int, split: bool) -> Tuple[torch.Tensor
     src = w.detach().contiguous()
     if src.dtype not in _DT:
         src = src.float()  # e.g. bfloat16 parameters handed to the fp16-operand build
-    n_out = src.shape[0]
+    rows = n_out = src.shape[0]
     if kind == L.PACK_CONV:
         n_in, ks = src.shape[1], src.shape[2]
         cols = n_in * ks * ks
+    elif kind == L.PACK_CONV_UP2:  # the four parity slabs [Cout][4 Cin] of the sub-pixel upsample conv, one after the other
+        n_in, ks = src.shape[1], src.shape[2]
+        rows, cols = 4 * n_out, 4 * n_in
     else:
         n_in, ks = src[0].numel(), 1
         cols = n_in
-    hi = torch.empty((n_out, cols), dtype=HALF, device=w.device)
+    hi = torch.empty((rows, cols), dtype=HALF, device=w.device)
     lo = torch.empty_like(hi) if split else None
     h = _h(w)
     L.check(L.load().crg_pack_weight(h, _st(), _p(src), _dt(src), kind, n_out, n_in, ks, _p(hi), _p(lo)), h, "crg_pack_weight")
@@ -792,13 +795,16 @@ def split_bf16(x: torch.Tensor):
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, padding=1,
            upsample2x: bool = False, x2: Optional[torch.Tensor] = None, cvec: Optional[torch.Tensor] = None,
            residual: Optional[torch.Tensor] = None, x_lo: Optional[torch.Tensor] = None, gn_stats: bool = False, gn=None,
-           x_mx: Optional[torch.Tensor] = None):
+           x_mx: Optional[torch.Tensor] = None, subpixel: Optional[bool] = None):
     """Implicit-GEMM conv over channels-last images.
     `gn` = (weight, bias, groups, eps, silu): also return silu?(GroupNorm(y)) - the norm that follows the conv inside a ResBlock
     (crg_conv_args.gn_y: on the small images of the two lowest UNet levels the launch that sums the K slices normalises as well);
     the call then returns (y, y_norm).  bf16 outputs only; anything else raises.
     padding: int (symmetric) or (top, left, bottom, right).  `upsample2x`: nearest-2x of the input is
-    folded into the gather.  `x2`: second half of a virtual channel concat.  `cvec` fp32 [N, Cout] is
+    folded into the gather - or, where upsample_subpixel_ok() holds and nothing else is fused, run as four 2x2 parity convs on the source
+    grid with pre-summed weights (4 / 9 of the multiplies).  `subpixel`: None = that form for fp32-class planes (`x_lo`) only, where
+    rounding the fp32 sum of the taps is the format's own rounding; a 16-bit conv keeps the gather form unless the caller passes True and so
+    accepts weights rounded to the operand type a second time (2e-3 of one conv's output); False = always the gather form.  `x2`: second half of a virtual channel concat.  `cvec` fp32 [N, Cout] is
     added per sample (timestep embedding); `residual` is added after.  `x_lo`: x is the bf16 hi plane of a pre-split
     fp32 activation and x_lo its lo plane (group_norm(split=True) / split_bf16): fp32-class conv with fp32 output.
     `gn_stats`: the output feeds a GroupNorm - emit its statistics side channel where the path supports it (bf16, see above).
@@ -842,7 +848,9 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         return y
     planes = x_lo is not None
     split = planes or x.dtype == torch.float32
-    hi, lo = packed_weight(weight, L.PACK_CONV, split)
+    up2 = bool(upsample2x) and (planes if subpixel is None else subpixel) and stride == 1 and (pt, pl, pb, pr) == (1, 1, 1, 1) and x2 is None and cvec is None and residual is None \
+        and gn is None and upsample_subpixel_ok(x, weight, x_lo)
+    hi, lo = packed_weight(weight, L.PACK_CONV_UP2 if up2 else L.PACK_CONV, split)
     y = empty_image(n, cout, ho, wo, torch.float32 if planes else x.dtype, x.device)
     if residual is not None:
         residual = to_channels_last(residual)
@@ -854,7 +862,7 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     a = L.ConvArgs(x=x.data_ptr(), x2=x2.data_ptr() if x2 is not None else None, C1=c1, C2=c2, w=hi.data_ptr(),
                    w_lo=lo.data_ptr() if lo is not None else None, bias=_p(f32_vec(bias)).value, cvec=_p(cvec).value,
                    cvec_ld=cvec.stride(0) if cvec is not None else 0, residual=_p(residual).value, y=y.data_ptr(), N=n, H=hh, W=ww, Cout=cout, Ho=ho, Wo=wo, ksize=ks, stride=stride,
-                   pad_t=pt, pad_l=pl, upsample2x=int(upsample2x), x_dtype=_act_dt(x), y_dtype=_act_dt(y),
+                   pad_t=pt, pad_l=pl, upsample2x=2 if up2 else int(upsample2x), x_dtype=_act_dt(x), y_dtype=_act_dt(y),
                    prec=L.PREC_BF16X3 if planes else _prec(x), x_lo=x_lo.data_ptr() if planes else None)
     y_norm = keep = None
     if gn is not None:
@@ -907,6 +915,24 @@ def _conv2d_mx(x16, x8, weight, bias, stride, padding, upsample2x, x2, cvec, res
     if stats is not None:
         y._crg_gn = (stats, y._version, hh * ww)
     return y
+
+
+UP_SUBPIX = __import__("os").environ.get("CRG_UP_SUBPIX", "1") != "0"  # dev knob (A/B): 0 = upsample convs keep the gather form
+
+
+def upsample_subpixel_ok(x: torch.Tensor, weight: torch.Tensor, x_lo: Optional[torch.Tensor] = None) -> bool:
+    """Can conv2d(x, weight, upsample2x=True[, x_lo=x_lo]) (3x3, stride 1, pad 1, no fusions; 16-bit x: subpixel=True) run in the sub-pixel form - four 2x2 convs
+    on the source grid with pre-summed weights (crg_conv_args.upsample2x = 2)?  Mirrors the native conditions: a 16-bit x plane (half-type
+    activations, or the hi / lo planes of an fp32 one), Cin % 64 == 0, Cout > 32, H * W a multiple of the 128-pixel tile and a source width
+    the row-halo kernel's buffers take (16..128 dividing 128, or a multiple of 128).  Everything else keeps the gather form."""
+    if not (UP_SUBPIX and x.is_cuda and x.dim() == 4 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+        return False
+    if x.dtype != HALF or (x_lo is not None and (x_lo.dtype != HALF or x_lo.shape != x.shape)):
+        return False
+    n, c, hh, ww = x.shape
+    if weight.shape[1] != c or c % 64 or weight.shape[0] <= 32:
+        return False
+    return (hh * ww) % 128 == 0 and ww >= 16 and (128 % ww == 0 if ww <= 128 else ww % 128 == 0)
 
 
 def mx_conv_ok(x: torch.Tensor, conv_weight: torch.Tensor) -> bool:

@@ -241,7 +241,12 @@ typedef struct {
   void* y;
   int N, H, W, Cout, Ho, Wo;
   int ksize, stride, pad_t, pad_l;  /* pad_b / pad_r are implied by Ho/Wo */
-  int upsample2x;
+  int upsample2x;                   /* 0: none; 1: nearest-2x of x folded into the gather (any shape the conv takes); 2: the SUB-PIXEL form
+                                       of the same conv - w / w_lo are the parity image (CRG_PACK_CONV_UP2) and each of the four output
+                                       parities is a 2x2 conv on the source grid, 4 / 9 of the multiplies.  Needs 3x3 / stride 1 / pad 1,
+                                       Ho = 2 H, Wo = 2 W, Cin % 64 == 0, Cout > 32, H * W % 128 == 0, W in {16, 32, 64, 128} or a multiple
+                                       of 128, 16-bit x (prec BF16 with 16-bit y, or BF16X3 on pre-split planes), and no x2 / cvec /
+                                       residual / gn_y; anything else is an error, not a fallback */
   int x_dtype, y_dtype, prec;
   const void* x_lo;                 /* BF16X3 with PRE-SPLIT activations: `x` is the bf16 hi plane, `x_lo` the bf16 lo plane
                                        (same layout; written by crg_groupnorm_split / crg_split_bf16); x_dtype = CRG_BF16,
@@ -275,8 +280,14 @@ int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* args);
  *                                                             [Cin/64][tap][64] (chunk-major: the 9 taps of one
  *                                                             64-channel slab are consecutive k-tiles -> L1 reuse)
  *   CRG_PACK_GEGLU    [2*F][K]          -> rows interleaved in 16-row groups [v0-15|g0-15|v16-31|..]
+ *   CRG_PACK_CONV_UP2 [Cout][Cin][3][3] -> [4][Cout][4*Cin]   the parity image of the conv behind a nearest-2x upsample
+ *                                                             (crg_conv_args.upsample2x = 2; Cin % 64 == 0): slab (a, b) holds, in
+ *                                                             K order [Cin/64][u][v][64], the sums of the taps W[kh][kw] that read
+ *                                                             source pixel (i + a - 1 + u, j + b - 1 + v) for output (2i + a, 2j + b):
+ *                                                             kh in {0},{1,2} (a = 0) or {0,1},{2} (a = 1) for u = 0, 1; kw likewise.
+ *                                                             Summed in fp32, then rounded (or split) once.  16 * Cout * Cin elements.
  * dst_hi (and dst_lo when non-NULL: the bf16 residual src - hi) are bf16, caller-allocated. */
-enum crg_pack_kind { CRG_PACK_LINEAR = 0, CRG_PACK_CONV = 1, CRG_PACK_GEGLU = 2 };
+enum crg_pack_kind { CRG_PACK_LINEAR = 0, CRG_PACK_CONV = 1, CRG_PACK_GEGLU = 2, CRG_PACK_CONV_UP2 = 3 };
 int crg_pack_weight(crg_ctx* ctx, void* stream, const void* src, int src_dtype, int kind, int n_out, int n_in,
                     int ksize, void* dst_hi, void* dst_lo);
 /* bias for GEGLU packed the same way (fp32 in, fp32 out) */
