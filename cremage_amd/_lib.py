@@ -95,6 +95,20 @@ class SamplerStepArgs(C.Structure):
     ]
 
 
+KSTEP_DPM2_2, KSTEP_SDE_1, KSTEP_SDE_2M, KSTEP_SDE_3M = range(4)  # CRG_KSTEP_*
+
+
+class KStepArgs(C.Structure):
+    _fields_ = [
+        ("kind", c_int), ("n", c_int64),
+        ("x", c_void_p), ("eps", c_void_p), ("x2", c_void_p), ("den_out", c_void_p), ("old", c_void_p * 2), ("noise", c_void_p),
+        ("c_out", c_float), ("cfg_scale", c_float), ("sigma", c_float), ("dt", c_float), ("sigma_up", c_float), ("s_noise", c_float),
+        ("m", c_float * 2), ("a", c_float), ("c1", c_float), ("c2", c_float), ("p", c_float * 2),
+        ("r", c_float * 2), ("rsum", c_float), ("phi2", c_float), ("phi3", c_float),
+        ("order", c_int), ("last", c_int), ("have_old", c_int), ("add_noise", c_int),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -149,6 +163,7 @@ SIGNATURES = {
     "crg_cfg_dpmpp2m_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                      c_float, c_int]),
     "crg_cfg_sampler_step": (c_int, [c_void_p, c_void_p, C.POINTER(SamplerStepArgs)]),
+    "crg_cfg_kstep": (c_int, [c_void_p, c_void_p, C.POINTER(KStepArgs)]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

@@ -735,6 +735,114 @@ extern "C" int crg_cfg_sampler_step(crg_ctx* ctx, void* stream, const crg_sample
   return 0;
 }
 
+namespace {
+// One fused evaluation step of the SD1.5 k-diffusion samplers cfg_sampler_step_kernel does not cover (see include/crg_hip.h,
+// crg_kstep_args): the same denoiser scalings and guidance, then the kind's update, one fp32 rounding per operation in the
+// reference's order (no FMA contraction).  Arguments by value; a buffer the kind or branch does not use is never dereferenced.
+__global__ __launch_bounds__(256) void cfg_kstep_kernel(crg_kstep_args a) {
+#pragma clang fp contract(off)
+  const long n = (long)a.n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float xv = a.x[i];
+    const float xin = a.kind == CRG_KSTEP_DPM2_2 ? a.x2[i] : xv;
+    const float den_u = a.eps[i] * a.c_out + xin;
+    const float den_c = a.eps[n + i] * a.c_out + xin;
+    const float den = den_u + a.cfg_scale * (den_c - den_u);
+    float xn = xv;
+    switch (a.kind) {
+      case CRG_KSTEP_DPM2_2: {
+        const float d2 = (xin - den) / a.sigma;
+        xn = xv + d2 * a.dt;
+        if (a.add_noise) xn = xn + (a.noise[i] * a.s_noise) * a.sigma_up;
+        break;
+      }
+      case CRG_KSTEP_SDE_1: {
+        float x2 = a.m[0] * xv - a.m[1] * den;
+        if (a.add_noise) x2 = x2 + (a.noise[i] * a.s_noise) * a.sigma_up;
+        a.x2[i] = x2;
+        continue;  // x is not written
+      }
+      case CRG_KSTEP_SDE_2M:
+      case CRG_KSTEP_SDE_3M: {
+        if (a.last) {
+          xn = den;
+        } else {
+          xn = a.a * xv + a.c1 * den;
+          if (a.kind == CRG_KSTEP_SDE_2M) {
+            if (a.have_old) xn = xn + a.c2 * (den - a.old[0][i]);
+          } else if (a.order == 2) {
+            const float d = (den - a.old[0][i]) / a.r[0];
+            xn = xn + a.phi2 * d;
+          } else if (a.order == 3) {
+            const float den1 = a.old[0][i];
+            const float d10 = (den - den1) / a.r[0];
+            const float d11 = (den1 - a.old[1][i]) / a.r[1];
+            const float dd = d10 - d11;
+            const float d1 = d10 + (dd * a.r[0]) / a.rsum;
+            const float d2 = dd / a.rsum;
+            xn = (xn + a.phi2 * d1) - a.phi3 * d2;
+          }
+          if (a.add_noise) xn = xn + ((a.noise[i] * a.p[0]) * a.p[1]) * a.s_noise;
+        }
+        a.den_out[i] = den;
+        break;
+      }
+      default:
+        break;
+    }
+    a.x[i] = xn;
+  }
+}
+}  // namespace
+
+extern "C" int crg_cfg_kstep(crg_ctx* ctx, void* stream, const crg_kstep_args* args) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, args != nullptr, "cfg_kstep: null args");
+  const crg_kstep_args& a = *args;
+  const int k = a.kind;
+  CRG_REQUIRE(ctx, k >= CRG_KSTEP_DPM2_2 && k <= CRG_KSTEP_SDE_3M, "cfg_kstep: unknown kind %d", k);
+  CRG_REQUIRE(ctx, a.n > 0 && a.x && a.eps, "cfg_kstep: empty input");
+  const bool multistep = k == CRG_KSTEP_SDE_2M || k == CRG_KSTEP_SDE_3M;
+  CRG_REQUIRE(ctx, k != CRG_KSTEP_DPM2_2 || a.sigma > 0.f, "cfg_kstep: DPM2_2 divides by sigma, which must be positive (got %g)",
+              (double)a.sigma);
+  CRG_REQUIRE(ctx, multistep || a.x2, "cfg_kstep: kind %d needs x2", k);
+  CRG_REQUIRE(ctx, multistep || (a.x2 != a.x), "cfg_kstep: kind %d: x2 must not alias x", k);
+  CRG_REQUIRE(ctx, !multistep || a.den_out, "cfg_kstep: kind %d needs den_out", k);
+  CRG_REQUIRE(ctx, !multistep || a.den_out != a.x, "cfg_kstep: kind %d: den_out must not alias x", k);
+  crg_kstep_args kargs = a;
+  kargs.last = multistep && a.last ? 1 : 0;
+  kargs.have_old = k == CRG_KSTEP_SDE_2M && !kargs.last && a.have_old ? 1 : 0;
+  kargs.order = k == CRG_KSTEP_SDE_3M && !kargs.last ? a.order : 1;
+  if (kargs.last) kargs.add_noise = 0;  // x = den: nothing else is read
+  kargs.add_noise = kargs.add_noise ? 1 : 0;
+  if (k == CRG_KSTEP_SDE_3M && !kargs.last) {
+    CRG_REQUIRE(ctx, a.order >= 1 && a.order <= 3, "cfg_kstep: SDE_3M order %d out of 1..3", a.order);
+    CRG_REQUIRE(ctx, a.order < 2 || a.r[0] != 0.f, "cfg_kstep: SDE_3M order %d divides by r0, which must not be 0", a.order);
+    CRG_REQUIRE(ctx, a.order < 3 || (a.r[1] != 0.f && a.rsum != 0.f), "cfg_kstep: SDE_3M order 3 divides by r1 and r0 + r1, which must not be 0");
+  }
+  const int n_old = kargs.have_old ? 1 : (k == CRG_KSTEP_SDE_3M ? kargs.order - 1 : 0);
+  for (int h = 0; h < n_old; ++h) {
+    CRG_REQUIRE(ctx, a.old[h] != nullptr, "cfg_kstep: kind %d reads old[%d], which is null", k, h);
+    CRG_REQUIRE(ctx, a.old[h] != a.den_out, "cfg_kstep: den_out must not alias old[%d]", h);
+  }
+  CRG_REQUIRE(ctx, !kargs.add_noise || a.noise, "cfg_kstep: add_noise needs a noise tensor");
+  for (int h = n_old; h < 2; ++h) kargs.old[h] = nullptr;  // nothing past what the branch reads
+  if (!kargs.add_noise) kargs.noise = nullptr;
+  if (multistep) kargs.x2 = nullptr; else kargs.den_out = nullptr;
+  // a written buffer must not start inside eps or be the noise tensor: another thread reads those
+  const float* const written[3] = {kargs.x, k == CRG_KSTEP_SDE_1 ? kargs.x2 : nullptr, kargs.den_out};
+  for (const float* w : written)
+    CRG_REQUIRE(ctx, !w || ((w < a.eps || w >= a.eps + 2 * a.n) && w != kargs.noise), "cfg_kstep: kind %d writes into eps or noise (alias)", k);
+  hipStream_t st = (hipStream_t)stream;
+  // both eps halves, the input and one store, plus what the kind adds
+  const double words = 4.0 + (k == CRG_KSTEP_DPM2_2 ? 1.0 : 0.0) + (multistep ? 1.0 + n_old : 0.0) +
+                       (kargs.add_noise ? 1.0 : 0.0);
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, (k == CRG_KSTEP_SDE_3M && kargs.order == 3 ? 22.0 : 12.0) * a.n, 4.0 * a.n * words);
+  hipLaunchKernelGGL(cfg_kstep_kernel, dim3(grid_for(a.n)), dim3(256), 0, st, kargs);
+  CRG_CHECK_LAUNCH(ctx, "cfg_kstep");
+  return 0;
+}
+
 extern "C" int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, n > 0, "axpby: empty");

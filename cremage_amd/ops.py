@@ -1167,6 +1167,45 @@ def cfg_sampler_step_(kind: str, x: torch.Tensor, eps2: torch.Tensor, c_out: flo
     return _written(x)
 
 
+KSTEP_KINDS = {"dpm2_2": L.KSTEP_DPM2_2, "sde_1": L.KSTEP_SDE_1, "sde_2m": L.KSTEP_SDE_2M, "sde_3m": L.KSTEP_SDE_3M}
+
+
+def cfg_kstep_(kind: str, x: torch.Tensor, eps2: torch.Tensor, c_out: float, cfg_scale: float, sigma: float = 0.0, dt: float = 0.0,
+               x2: Optional[torch.Tensor] = None, den_out: Optional[torch.Tensor] = None, old=(), noise: Optional[torch.Tensor] = None,
+               sigma_up: float = 0.0, s_noise: float = 1.0, m=(0.0, 0.0), a: float = 0.0, c1: float = 0.0, c2: float = 0.0,
+               p=(0.0, 0.0), r=(0.0, 0.0), rsum: float = 0.0, phi2: float = 0.0, phi3: float = 0.0, order: int = 1, last: bool = False,
+               have_old: bool = False, add_noise: bool = False) -> torch.Tensor:
+    """Fused evaluation step of the SD1.5 k-diffusion samplers (crg_cfg_kstep, one launch): `kind` one of KSTEP_KINDS; x fp32 [b, ...],
+    eps2 fp32 [2b, ...] (the raw network output, uncond half first); x2 / den_out / old / noise fp32 [b, ...] as the kind reads or
+    writes them (see include/crg_hip.h); the scalars are the fp32 values the reference's per-step tensors hold.  Returns x."""
+    bufs = [x2, den_out, noise] + list(old)
+    _need_cuda(x, eps2, *bufs)
+    if kind not in KSTEP_KINDS or len(old) > 2:
+        raise L.CrgError(f"cfg_kstep_: unknown kind {kind!r} or more than 2 history buffers")
+    if x.dtype != torch.float32 or eps2.dtype != torch.float32 or not x.is_contiguous() or not eps2.is_contiguous() \
+            or eps2.numel() != 2 * x.numel() or any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                                                                       or t.numel() != x.numel()) for t in bufs):
+        raise L.CrgError("cfg_kstep_: contiguous fp32 x [b,...], eps [2b,...] and [b,...] side buffers expected")
+    k = L.KStepArgs()
+    k.kind, k.n = KSTEP_KINDS[kind], x.numel()
+    k.x, k.eps, k.x2, k.den_out, k.noise = _p(x), _p(eps2), _p(x2), _p(den_out), _p(noise)
+    for j, t in enumerate(old):
+        k.old[j] = _p(t)
+    k.c_out, k.cfg_scale, k.sigma, k.dt, k.sigma_up, k.s_noise = (float(v) for v in (c_out, cfg_scale, sigma, dt, sigma_up, s_noise))
+    k.a, k.c1, k.c2, k.rsum, k.phi2, k.phi3 = (float(v) for v in (a, c1, c2, rsum, phi2, phi3))
+    for j in range(2):
+        k.m[j], k.p[j], k.r[j] = float(m[j]), float(p[j]), float(r[j])
+    k.order, k.last, k.have_old, k.add_noise = int(order), 1 if last else 0, 1 if have_old else 0, 1 if add_noise else 0
+    h = _h(x)
+    L.check(L.load().crg_cfg_kstep(h, _st(), C.byref(k)), h, "crg_cfg_kstep")
+    if kind == "sde_1":  # writes x2 only
+        _written(x2)
+        return x
+    if den_out is not None and kind != "dpm2_2":
+        _written(den_out)
+    return _written(x)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

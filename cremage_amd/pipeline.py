@@ -14,6 +14,7 @@ Step structure reproduced (file:line of the reference):
 """
 from __future__ import annotations
 
+import functools
 from typing import Callable, Optional
 
 import numpy as np
@@ -23,6 +24,7 @@ from . import ops
 from .ldm_hip.latent_diffusion import LatentDiffusion, LatentInpaintDiffusion
 from .ldm_hip.unet import UNetModel
 from .ldm_hip.vae import AutoencoderKL
+from . import samplers as K
 from .samplers import DDIMSampler, EulerAncestralSampler, EulerSampler
 from .synth import synth_fill_
 
@@ -33,6 +35,16 @@ SD15_VAE_DD = dict(double_z=True, z_channels=4, resolution=256, in_channels=3, o
                    num_res_blocks=2, attn_resolutions=[], dropout=0.0)  # v1-inference.yaml:51-65
 
 SAMPLERS = {"euler": EulerSampler, "euler_a": EulerAncestralSampler}  # sampler_utils.py:36-66 names "Euler", "Euler a"
+# the rest of the menu: one table-driven class (samplers.KSampler), a constructor per key
+SAMPLERS.update({key: functools.partial(K.KSampler, key=key) for key in K.K_SAMPLER_KEYS})
+
+
+def _sampler(name: str):
+    """(key, sampler constructor) of a SAMPLERS key or Cremage's menu name ("DPM++ 2M", ...)."""
+    key = K.sampler_key(name)
+    if key not in SAMPLERS:
+        raise ValueError(f"sampler {name!r} is not a k-diffusion sampler (one of {sorted(SAMPLERS)}): DDIM runs through img2img / inpaint")
+    return key, SAMPLERS[key]
 
 
 def build_synthetic_ldm(unet_cfg=None, vae_dd=None, device="cuda", unet_dtype=torch.bfloat16, vae_dtype=torch.float32,
@@ -136,9 +148,11 @@ def txt2img(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tensor], *
     (image_generator.py:795-808).  `generators`: one torch.Generator per image (seed + global image index, cremage_amd.dist.image_seed):
     the initial latents (unless x0 is given) and the ancestral noise of image i come from generators[i], so that a batch sharded over
     GPUs draws what the unsharded batch draws.  Without an explicit `noise_sampler` the ancestral sampler's noise is drawn once per run
-    (trajectory_noise_sampler)."""
+    (trajectory_noise_sampler).  `sampler`: a SAMPLERS key or Cremage's menu name; the table-driven samplers that draw noise get a
+    trajectory_noise_sampler sized by their plan's draw count, DPM++ SDE a samplers.BrownianPairNoise (per image with `generators`)."""
     b = c.shape[0]
     dev = c.device
+    sampler, make = _sampler(sampler)
     if x0 is None and generators is not None:
         x0 = torch.stack([torch.randn((4, height // 8, width // 8), generator=g, device=dev) for g in generators])
     if noise_sampler is None and sampler == "euler_a" and dev.type == "cuda":
@@ -147,7 +161,13 @@ def txt2img(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tensor], *
         c = {"c_crossattn": [c], "c_concat": [hint]}
         uc = {"c_crossattn": [uc], "c_concat": [hint]} if uc is not None else None
     shape = [4, height // 8, width // 8]
-    smp = SAMPLERS[sampler](ldm)
+    smp = make(ldm)
+    if noise_sampler is None and sampler in K.K_SAMPLER_KEYS and dev.type == "cuda":
+        if sampler == "dpmpp_sde":
+            noise_sampler = K.BrownianPairNoise((b, *shape), dev, generators=generators)
+        else:
+            draws = K.plan_draws(smp.plan(steps))
+            noise_sampler = trajectory_noise_sampler(draws, (b, *shape), dev, generators) if draws else None
     smp.noise_sampler = noise_sampler
     samples, _ = smp.sample(S=steps, conditioning=c, batch_size=b, shape=shape, verbose=False,
                             unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x0=x0)
@@ -161,10 +181,11 @@ def txt2img_hires(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tens
                   decode: bool = True):
     """Hires-fix with the latent upscaler (image_generator.py:958-999): txt2img at (height, width); bilinear upscale of the final
     latents by `factor`; forward-diffuse to t_enc = int(strength * steps) (k_diffusion_samplers.py:255-296) and denoise the last
-    t_enc + 1 sigmas at the larger size (img2img_sampling :227-246).  Returns (images, latents, base latents)."""
+    t_enc + 1 sigmas at the larger size (img2img_sampling :227-246).  `sampler`: a SAMPLERS key or Cremage's menu name.  Returns
+    (images, latents, base latents)."""
     import torch.nn.functional as F
     b = c.shape[0]
-    smp = SAMPLERS[sampler](ldm)
+    smp = _sampler(sampler)[1](ldm)
     smp.noise_sampler = noise_sampler
     base, _ = smp.sample(S=steps, conditioning=c, batch_size=b, shape=[4, height // 8, width // 8], verbose=False,
                          unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x0=x0)

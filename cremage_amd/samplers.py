@@ -440,6 +440,445 @@ class EulerAncestralSampler(KDiffusionSamplerBase):
                                       sigmas_host=self.sigmas_host), None
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# The rest of Cremage's SD1.5 sampler menu (cremage/utils/sampler_utils.py:21-34): Heun, DPM2, DPM2 A, LMS, DPM++ 2S A, DPM++ SDE,
+# DPM++ 2M, DPM++ 2M SDE, DPM++ 3M SDE (k_diffusion sampling.py:166-285, :516-710 behind k_diffusion_samplers.py:321-411).  A run is a
+# PLAN: the list of its UNet evaluations, built on the CPU from the host fp32 schedule, each with its sigma, the kind of update that
+# follows it, that update's scalars (Python floats holding the fp32 values of the reference's own torch expressions on 0-dim CPU
+# tensors, op for op) and the noise draw it makes.  Two executors run a plan through one loop (run_plan): torch arithmetic with one
+# fp32 rounding per reference operation, or one fused HIP launch per evaluation.
+
+def get_sigmas_karras(n, sigma_min=0.0316386, sigma_max=14.5521805, rho=7., device='cpu'):
+    """The Karras et al. schedule followed by 0 (k_diffusion sampling.py:17-23), computed on the CPU in fp32 whatever `device`, so the
+    sigmas equal those of a CPU run of the reference bit for bit; the expression is sgm_hip.sampling.EDMDiscretization's."""
+    from .sgm_hip.sampling import EDMDiscretization
+    return EDMDiscretization(sigma_min, sigma_max, rho)(n, do_append_zero=True, device=device)
+
+
+def _t_fn(sigma):
+    return sigma.log().neg()
+
+
+def _sigma_fn(t):
+    return t.neg().exp()
+
+
+def _entry(sigma, kind, draw=None, **scalars):
+    """One UNet evaluation of a plan: its sigma, the update kind that consumes it, (sigma, sigma_next) of the noise draw made with it
+    (None: no draw) and the kind's scalars."""
+    return dict(sigma=float(sigma), kind=kind, draw=None if draw is None else (float(draw[0]), float(draw[1])), **scalars)
+
+
+def plan_heun(sh, eta=1., s_noise=1.):
+    """sample_heun with churn 0 (sampling.py:166-192): sigma_hat == sigma.  `tick`: the step's unused torch.randn_like draw (:173)."""
+    from .sgm_hip.sampling import edm_table
+    plan = []
+    for r in edm_table(sh, 1):
+        plan.append(_entry(r["sigma_hat"], "heun_1", dt=r["dt"], one_call=not r["two_call"], tick=True))
+        if r["two_call"]:
+            plan.append(_entry(r["next"], "heun_2", dt=r["dt"]))
+    return plan
+
+
+def _plan_dpm2(sh, ancestral, eta, s_noise):
+    plan = []
+    for i in range(len(sh) - 1):
+        s, sn = sh[i], sh[i + 1]
+        target, up = get_ancestral_step(s, sn, eta=eta) if ancestral else (sn, 0.)
+        if target == 0:  # Euler
+            plan.append(_entry(s, "heun_1", dt=float(target - s), one_call=True, tick=not ancestral))
+            continue
+        mid = s.log().lerp(target.log(), 0.5).exp()
+        plan.append(_entry(s, "heun_1", dt=float(mid - s), one_call=False, tick=not ancestral))
+        plan.append(_entry(mid, "dpm2_2", dt=float(target - s), draw=(s, sn) if ancestral else None, sigma_up=float(up), s_noise=s_noise))
+    return plan
+
+
+def plan_dpm2(sh, eta=1., s_noise=1.):
+    """sample_dpm_2 with churn 0 (sampling.py:195-223): an Euler step to the log-midpoint sigma, then the midpoint derivative."""
+    return _plan_dpm2(sh, False, eta, s_noise)
+
+
+def plan_dpm2_a(sh, eta=1., s_noise=1.):
+    """sample_dpm_2_ancestral (sampling.py:226-252): DPM2 toward sigma_down; noise on the two-call steps only."""
+    return _plan_dpm2(sh, True, eta, s_noise)
+
+
+def plan_lms(sh, eta=1., s_noise=1., order=4):
+    """sample_lms (sampling.py:268-285), order 4; the coefficients are sgm_hip.sampling.lms_table's (no scipy)."""
+    from .sgm_hip.sampling import lms_table
+    return [_entry(sh[i], "lms", coef=list(coef)) for i, coef in enumerate(lms_table(sh, order))]
+
+
+def plan_dpmpp_2s_a(sh, eta=1., s_noise=1.):
+    """sample_dpmpp_2s_ancestral (sampling.py:516-547); the scalars are sgm_hip.sampling.ancestral_table's (the same expressions)."""
+    from .sgm_hip.sampling import ancestral_table
+    plan = []
+    for r in ancestral_table(sh, 1, eta):
+        draw = (r["sigma"], r["next"]) if r["next"] > 0 else None
+        noisy = dict(draw=draw, sigma_up=r["sigma_up"], s_noise=s_noise)
+        if not r["two_call"]:
+            plan.append(_entry(r["sigma"], "dpmpp2s_1", dt=r["dt"], one_call=True, **noisy))
+            continue
+        plan.append(_entry(r["sigma"], "dpmpp2s_1", m=r["m"], one_call=False))
+        plan.append(_entry(r["s_sigma"], "dpmpp2s_2", m=r["m"], **noisy))
+    return plan
+
+
+def plan_dpmpp_sde(sh, eta=1., s_noise=1., r=0.5):
+    """sample_dpmpp_sde (sampling.py:550-589) with r = 1/2: fac = 1, so denoised_d is the second evaluation's value and step 2 is
+    DPM++ 2S's second update with the SDE's multipliers.  Both draws of a step start at sigma_fn(t)."""
+    plan = []
+    for i in range(len(sh) - 1):
+        if sh[i + 1] == 0:  # Euler, no noise
+            plan.append(_entry(sh[i], "heun_1", dt=float(sh[i + 1] - sh[i]), one_call=True))
+            continue
+        t, t_next = _t_fn(sh[i]), _t_fn(sh[i + 1])
+        h = t_next - t
+        s = t + h * r
+        sd, su = get_ancestral_step(_sigma_fn(t), _sigma_fn(s), eta)
+        s_ = _t_fn(sd)
+        plan.append(_entry(sh[i], "sde_1", m=[float(_sigma_fn(s_) / _sigma_fn(t)), float((t - s_).expm1())], sigma_up=float(su),
+                           s_noise=s_noise, draw=(_sigma_fn(t), _sigma_fn(s))))
+        sd, su = get_ancestral_step(_sigma_fn(t), _sigma_fn(t_next), eta)
+        t_next_ = _t_fn(sd)
+        plan.append(_entry(_sigma_fn(s), "dpmpp2s_2", m=[0., 0., float(_sigma_fn(t_next_) / _sigma_fn(t)), float((t - t_next_).expm1())],
+                           sigma_up=float(su), s_noise=s_noise, draw=(_sigma_fn(t), _sigma_fn(t_next))))
+    return plan
+
+
+def plan_dpmpp_2m(sh, eta=1., s_noise=1.):
+    """sample_dpmpp_2m (sampling.py:592-615); the multipliers are sgm_hip.sampling.dpmpp2m_multipliers' (the same expressions)."""
+    from .sgm_hip.sampling import dpmpp2m_multipliers
+    return [_entry(sh[i], "dpmpp2m", m=[m1, m2, 0. if m3 is None else m3, 0. if m4 is None else m4], advanced=bool(adv))
+            for i, (m1, m2, m3, m4, adv) in enumerate(dpmpp2m_multipliers(sh))]
+
+
+def plan_dpmpp_2m_sde(sh, eta=1., s_noise=1.):
+    """sample_dpmpp_2m_sde, midpoint solver (sampling.py:618-660).  At ONE step the reference raises UnboundLocalError (its `h` is
+    never set); here a run whose first step already goes to sigma 0 returns the denoised value, as its longer runs end."""
+    plan, h_last = [], None
+    for i in range(len(sh) - 1):
+        if sh[i + 1] == 0:
+            plan.append(_entry(sh[i], "sde_2m", last=True))
+            continue
+        t, s = -sh[i].log(), -sh[i + 1].log()
+        h = s - t
+        eta_h = eta * h
+        c1 = (-h - eta_h).expm1().neg()
+        e = _entry(sh[i], "sde_2m", last=False, a=float(sh[i + 1] / sh[i] * (-eta_h).exp()), c1=float(c1), have_old=i > 0, s_noise=s_noise)
+        if i > 0:
+            e["c2"] = float(0.5 * c1 * (1 / (h_last / h)))
+        if eta:
+            e.update(draw=(float(sh[i]), float(sh[i + 1])), p=[float(sh[i + 1]), float((-2 * eta_h).expm1().neg().sqrt())])
+        plan.append(e)
+        h_last = h
+    return plan
+
+
+def plan_dpmpp_3m_sde(sh, eta=1., s_noise=1.):
+    """sample_dpmpp_3m_sde (sampling.py:663-710): first, second, then third order over the last two denoised values.  One step: as
+    plan_dpmpp_2m_sde (the reference raises there), the denoised value."""
+    plan, h_1, h_2 = [], None, None
+    for i in range(len(sh) - 1):
+        if sh[i + 1] == 0:
+            plan.append(_entry(sh[i], "sde_3m", last=True))
+            continue
+        t, s = -sh[i].log(), -sh[i + 1].log()
+        h = s - t
+        h_eta = h * (eta + 1)
+        e = _entry(sh[i], "sde_3m", last=False, a=float(torch.exp(-h_eta)), c1=float((-h_eta).expm1().neg()), order=1, s_noise=s_noise)
+        if h_1 is not None:
+            phi_2 = h_eta.neg().expm1() / h_eta + 1
+            e.update(order=2, r=[float(h_1 / h), 0.], phi2=float(phi_2))
+        if h_2 is not None:
+            r0, r1 = h_1 / h, h_2 / h
+            e.update(order=3, r=[float(r0), float(r1)], rsum=float(r0 + r1), phi3=float(phi_2 / h_eta - 0.5))
+        if eta:
+            e.update(draw=(float(sh[i]), float(sh[i + 1])), p=[float(sh[i + 1]), float((-2 * h * eta).expm1().neg().sqrt())])
+        plan.append(e)
+        h_1, h_2 = h, h_1
+    return plan
+
+
+# key -> (plan function, schedule): "model" = CompVisDenoiser.get_sigmas, "karras" = get_sigmas_karras (k_diffusion_samplers.py:321-411)
+K_SAMPLERS = {"heun": (plan_heun, "model"), "dpm2": (plan_dpm2, "karras"), "dpm2_a": (plan_dpm2_a, "karras"), "lms": (plan_lms, "model"),
+              "dpmpp_2s_a": (plan_dpmpp_2s_a, "karras"), "dpmpp_sde": (plan_dpmpp_sde, "karras"), "dpmpp_2m": (plan_dpmpp_2m, "karras"),
+              "dpmpp_2m_sde": (plan_dpmpp_2m_sde, "karras"), "dpmpp_3m_sde": (plan_dpmpp_3m_sde, "karras")}
+K_SAMPLER_KEYS = tuple(K_SAMPLERS)
+# Cremage's SD1.5 sampler menu (cremage/utils/sampler_utils.py:21-34) -> keys
+CREMAGE_SD15_SAMPLER_KEYS = {"DDIM": "ddim", "Euler": "euler", "Euler A": "euler_a", "Heun": "heun", "DPM2": "dpm2", "DPM2 A": "dpm2_a",
+                             "LMS": "lms", "DPM++ 2S A": "dpmpp_2s_a", "DPM++ SDE": "dpmpp_sde", "DPM++ 2M": "dpmpp_2m",
+                             "DPM++ 2M SDE": "dpmpp_2m_sde", "DPM++ 3M SDE": "dpmpp_3m_sde"}
+
+
+def sampler_key(name: str) -> str:
+    """A sampler key, or Cremage's menu name for it ("DPM++ 2M SDE", ...), -> the key."""
+    key = CREMAGE_SD15_SAMPLER_KEYS.get(name, name)
+    if key not in CREMAGE_SD15_SAMPLER_KEYS.values():
+        raise ValueError(f"unknown SD1.5 sampler {name!r} (one of {list(CREMAGE_SD15_SAMPLER_KEYS)} or {list(CREMAGE_SD15_SAMPLER_KEYS.values())})")
+    return key
+
+
+def build_plan(key: str, sigmas_host, eta=1., s_noise=1.):
+    """The plan of sampler `key` over the host schedule (CPU fp32, ending in 0)."""
+    return K_SAMPLERS[key][0](sigmas_host.detach().to("cpu", torch.float32), eta=eta, s_noise=s_noise)
+
+
+def plan_draws(plan) -> int:
+    """How often a run of the plan calls its noise sampler."""
+    return sum(1 for e in plan if e["draw"] is not None)
+
+
+class BrownianPairNoise:
+    """Default noise of DPM++ SDE, whose two draws of a step cover overlapping sigma intervals that start at the same sigma: the
+    increments of ONE Brownian motion over [sigma_i, sigma_s] and [sigma_i, sigma_next], each divided by the root of its length, are
+    unit Gaussians with correlation rho = sqrt((sigma_i - sigma_s) / (sigma_i - sigma_next)).  A call that starts where the previous
+    one started and reaches further returns rho * z1 + sqrt(1 - rho^2) * z'; any other call a fresh draw.  The joint distribution is
+    that of the reference's BrownianTreeNoiseSampler; its torchsde random stream is not reproduced.  `generators`: one per image."""
+
+    def __init__(self, shape, device, dtype=torch.float32, generators=None):
+        self.shape, self.device, self.dtype, self.generators = tuple(shape), device, dtype, generators
+        self.prev = None  # (start sigma, end sigma, z)
+
+    def draw(self):
+        if self.generators is not None:
+            return torch.stack([torch.randn(self.shape[1:], generator=g, device=self.device, dtype=self.dtype) for g in self.generators])
+        return torch.randn(self.shape, device=self.device, dtype=self.dtype)
+
+    def __call__(self, sigma, sigma_next):
+        s0, s1 = float(sigma), float(sigma_next)
+        z = self.draw()
+        if self.prev is not None and self.prev[0] == s0 and s1 < self.prev[1] < s0:
+            rho2 = (s0 - self.prev[1]) / (s0 - s1)
+            z = rho2 ** 0.5 * self.prev[2] + (1.0 - rho2) ** 0.5 * z
+        self.prev = (s0, s1, z)
+        return z
+
+
+def _add_noise(x, z, e):
+    return x + z * e["s_noise"] * e["sigma_up"]
+
+
+def _div(a, v: float):
+    """a / v as the reference divides: by a 0-dim tensor on a's device, a correctly rounded division.  With a Python number (or a
+    0-dim CPU tensor) as the divisor PyTorch's device kernel multiplies by the reciprocal, which differs in the last bit."""
+    return a / torch.full((), v, dtype=a.dtype, device=a.device)
+
+
+class _TorchSteps:
+    """A plan's updates in torch arithmetic, one fp32 rounding per reference operation: any device, any denoiser `model(x, sigma)`."""
+
+    def __init__(self, model, x):
+        self.model, self.x = model, x
+        self.x2 = self.d = None
+        self.hist = []  # LMS: derivatives, the multistep samplers: denoised values; newest first
+
+    def step(self, k, e, z):
+        xin = self.x2 if e["kind"] in ("heun_2", "dpm2_2", "dpmpp2s_2") else self.x
+        den = self.model(xin, torch.full((xin.shape[0],), e["sigma"], dtype=torch.float32, device=xin.device))
+        getattr(self, "_" + e["kind"])(e, den, z)
+
+    def _heun_1(self, e, den, z):
+        d = _div(self.x - den, e["sigma"])
+        x2 = self.x + d * e["dt"]
+        if e["one_call"]:
+            self.x = x2
+        else:
+            self.x2, self.d = x2, d
+
+    def _heun_2(self, e, den, z):
+        d2 = _div(self.x2 - den, e["sigma"])
+        self.x = self.x + ((self.d + d2) / 2) * e["dt"]
+
+    def _dpm2_2(self, e, den, z):
+        d2 = _div(self.x2 - den, e["sigma"])
+        self.x = self.x + d2 * e["dt"]
+        if z is not None:
+            self.x = _add_noise(self.x, z, e)
+
+    def _lms(self, e, den, z):
+        self.hist = [_div(self.x - den, e["sigma"])] + self.hist[:len(e["coef"]) - 1]
+        self.x = self.x + sum(c * d for c, d in zip(e["coef"], self.hist))
+
+    def _dpmpp2s_1(self, e, den, z):
+        if not e["one_call"]:
+            self.x2 = e["m"][0] * self.x - e["m"][1] * den
+            return
+        self.x = self.x + _div(self.x - den, e["sigma"]) * e["dt"]
+        if z is not None:
+            self.x = _add_noise(self.x, z, e)
+
+    def _dpmpp2s_2(self, e, den, z):
+        self.x = e["m"][2] * self.x - e["m"][3] * den
+        if z is not None:
+            self.x = _add_noise(self.x, z, e)
+
+    def _sde_1(self, e, den, z):
+        self.x2 = _add_noise(e["m"][0] * self.x - e["m"][1] * den, z, e)
+
+    def _dpmpp2m(self, e, den, z):
+        m1, m2, m3, m4 = e["m"]
+        self.x = m1 * self.x - m2 * ((m3 * den - m4 * self.hist[0]) if e["advanced"] else den)
+        self.hist = [den]
+
+    def _multistep(self, e, den, z, x):
+        if z is not None:
+            x = x + z * e["p"][0] * e["p"][1] * e["s_noise"]
+        self.x, self.hist = x, [den] + self.hist[:1]
+
+    def _sde_2m(self, e, den, z):
+        if e["last"]:
+            return self._multistep(e, den, None, den)
+        x = e["a"] * self.x + e["c1"] * den
+        if e["have_old"]:
+            x = x + e["c2"] * (den - self.hist[0])
+        self._multistep(e, den, z, x)
+
+    def _sde_3m(self, e, den, z):
+        if e["last"]:
+            return self._multistep(e, den, None, den)
+        x = e["a"] * self.x + e["c1"] * den
+        if e["order"] == 2:
+            x = x + e["phi2"] * _div(den - self.hist[0], e["r"][0])
+        elif e["order"] == 3:
+            r0, r1 = e["r"]
+            d1_0, d1_1 = _div(den - self.hist[0], r0), _div(self.hist[0] - self.hist[1], r1)
+            d1 = d1_0 + _div((d1_0 - d1_1) * r0, e["rsum"])
+            d2 = _div(d1_0 - d1_1, e["rsum"])
+            x = x + e["phi2"] * d1 - e["phi3"] * d2
+        self._multistep(e, den, z, x)
+
+
+class _FusedSteps:
+    """A plan's updates as one fused HIP launch per evaluation (crg_cfg_sampler_step, crg_cfg_dpmpp2m_step, crg_cfg_kstep), under
+    the conditions of LDMWrapperForKDiffusion.fused_step_ok.  Every evaluation sigma of the run goes through eps_tables once and the
+    UNet's timestep work is hoisted over the whole table; per evaluation one eps_pair_pre input build, the UNet and one step launch.
+    c_out is the exact -sigma (CompVisDenoiser does not snap it).  Works on a copy of x."""
+
+    def __init__(self, model, x, plan):
+        self.model, self.cfg = model, model.unconditional_guidance_scale
+        self.x = x.clone().contiguous()  # updated in place
+        c_in_all, t_all = model.eps_tables(torch.tensor([e["sigma"] for e in plan], dtype=torch.float32))
+        self.c_in = c_in_all
+        self.t_rows = _with_time_rows(model, t_all.reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous())
+        kinds = {e["kind"] for e in plan}
+        self.x2 = torch.empty_like(self.x) if kinds & {"heun_2", "dpm2_2", "dpmpp2s_2"} else None
+        self.d = torch.empty_like(self.x) if kinds & {"heun_2", "dpm2_2"} else None
+        n_ring = 4 if "lms" in kinds else 3 if "sde_3m" in kinds else 2 if "sde_2m" in kinds else 1 if "dpmpp2m" in kinds else 0
+        self.ring, self.n = [torch.empty_like(self.x) for _ in range(n_ring)], 0  # n: multistep evaluations so far
+
+    def step(self, k, e, z):
+        from . import ops
+        second = e["kind"] in ("heun_2", "dpm2_2", "dpmpp2s_2")
+        eps2 = self.model.eps_pair_pre(self.x2 if second else self.x, self.c_in[k], self.t_rows[k]).contiguous()
+        noisy = {} if z is None else dict(noise=z.contiguous(), s_noise=e["s_noise"], add_noise=True)
+        getattr(self, "_" + e["kind"])(ops, e, (self.x, eps2, -e["sigma"], self.cfg), noisy)
+
+    def _heun_1(self, ops, e, head, noisy):
+        ops.cfg_sampler_step_("heun_1", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, d=self.d, one_call=e["one_call"])
+
+    def _heun_2(self, ops, e, head, noisy):
+        ops.cfg_sampler_step_("heun_2", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, d=self.d)
+
+    def _dpmpp2s_1(self, ops, e, head, noisy):
+        if e["one_call"]:
+            ops.cfg_sampler_step_("dpmpp2s_1", *head, sigma=e["sigma"], dt=e["dt"], one_call=True, sigma_up=e["sigma_up"], **noisy)
+        else:
+            ops.cfg_sampler_step_("dpmpp2s_1", *head, x2=self.x2, m=e["m"])
+
+    def _dpmpp2s_2(self, ops, e, head, noisy):
+        ops.cfg_sampler_step_("dpmpp2s_2", *head, x2=self.x2, m=e["m"], sigma_up=e["sigma_up"], **noisy)
+
+    def _lms(self, ops, e, head, noisy):
+        n, self.n = self.n, self.n + 1
+        hist = [self.ring[(n - j) % 4] for j in range(1, len(e["coef"]))]
+        ops.cfg_sampler_step_("lms", *head, sigma=e["sigma"], d=self.ring[n % 4], hist=hist, coef=e["coef"])
+
+    def _dpmpp2m(self, ops, e, head, noisy):
+        ops.cfg_dpmpp2m_step_(head[0], head[1], self.ring[0], head[2], head[3], *e["m"], e["advanced"])
+
+    def _dpm2_2(self, ops, e, head, noisy):
+        ops.cfg_kstep_("dpm2_2", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, sigma_up=e["sigma_up"], **noisy)
+
+    def _sde_1(self, ops, e, head, noisy):
+        ops.cfg_kstep_("sde_1", *head, x2=self.x2, m=e["m"], sigma_up=e["sigma_up"], **noisy)
+
+    def _multistep(self, ops, e, head, noisy, n_old, **scalars):
+        """This step's denoised value goes to the ring slot the step does not read; `n_old` previous ones are handed over, newest first."""
+        n, self.n, r = self.n, self.n + 1, len(self.ring)
+        ops.cfg_kstep_(e["kind"], *head, den_out=self.ring[n % r], old=[self.ring[(n - j) % r] for j in range(1, n_old + 1)],
+                       last=e["last"], **scalars, **noisy)
+
+    def _sde_2m(self, ops, e, head, noisy):
+        if e["last"]:
+            return self._multistep(ops, e, head, {}, 0)
+        self._multistep(ops, e, head, noisy, int(e["have_old"]), a=e["a"], c1=e["c1"], c2=e.get("c2", 0.), p=e.get("p", (0., 0.)),
+                        have_old=e["have_old"])
+
+    def _sde_3m(self, ops, e, head, noisy):
+        if e["last"]:
+            return self._multistep(ops, e, head, {}, 0)
+        self._multistep(ops, e, head, noisy, e["order"] - 1, a=e["a"], c1=e["c1"], p=e.get("p", (0., 0.)), r=e.get("r", (0., 0.)),
+                        rsum=e.get("rsum", 0.), phi2=e.get("phi2", 0.), phi3=e.get("phi3", 0.), order=e["order"])
+
+
+@torch.no_grad()
+def run_plan(model, x, plan, noise_sampler=None, fused=None):
+    """Run a plan from x (not mutated): per evaluation the noise draw it makes - `noise_sampler(sigma, sigma_next)` with 0-dim CPU fp32
+    tensors, in the order, number and with the arguments of the reference's own calls; torch.randn_like by default - then the
+    evaluation and its update.  `fused`: None = whenever model.fused_step_ok(x), False = the torch executor."""
+    if noise_sampler is None:
+        noise_sampler = default_noise_sampler(x)
+    if fused is None:
+        fused = getattr(model, "fused_step_ok", lambda _x: False)(x)
+    ex = _FusedSteps(model, x, plan) if fused else _TorchSteps(model, x)
+    for k, e in enumerate(plan):
+        if e.get("tick"):
+            torch.randn_like(x)  # keeps the global RNG stream where the reference leaves it (see sample_euler)
+        z = noise_sampler(torch.tensor(e["draw"][0]), torch.tensor(e["draw"][1])) if e["draw"] is not None else None
+        ex.step(k, e, z)
+    return ex.x
+
+
+class KSampler(KDiffusionSamplerBase):
+    """The nine table-driven samplers as one class: `key` one of K_SAMPLER_KEYS picks the plan function and the schedule (the model's
+    get_sigmas, or Karras with the base class' sigma_min / sigma_max and rho 7).  `sample(denoising_steps=)` and stochastic_encode are
+    the base class', so hires-fix and partial denoising work as for Euler.  `noise_sampler` None: torch.randn_like per draw -
+    DPM++ 2M SDE / 3M SDE draw once per step over disjoint sigma intervals, which equals the reference's Brownian tree in
+    distribution - and BrownianPairNoise for DPM++ SDE.  No sampler here reproduces the reference's torchsde random stream."""
+
+    def __init__(self, model, key, eta=1., s_noise=1., fused=None, **kwargs):
+        if key not in K_SAMPLERS:
+            raise ValueError(f"unknown k-sampler {key!r} (one of {list(K_SAMPLERS)})")
+        super().__init__(model, **kwargs)
+        self.key, self.eta, self.s_noise, self.fused = key, eta, s_noise, fused
+
+    def compute_sigmas_host(self, n):
+        if K_SAMPLERS[self.key][1] == "karras":
+            return get_sigmas_karras(n, self.sigma_min, self.sigma_max)
+        return super().compute_sigmas_host(n)
+
+    @torch.no_grad()
+    def compute_sigmas(self, n):
+        if K_SAMPLERS[self.key][1] == "karras":
+            return get_sigmas_karras(n, self.sigma_min, self.sigma_max, device=self.device)
+        return self.compviz_wrapper_model.get_sigmas(n).to(self.device)
+
+    def plan(self, n, denoising_steps=None):
+        """The plan of an n-step schedule, or of its last `denoising_steps` steps."""
+        sh = self.compute_sigmas_host(n)
+        return build_plan(self.key, sh if denoising_steps is None else sh[-(denoising_steps + 1):], self.eta, self.s_noise)
+
+    @torch.no_grad()
+    def do_sample(self):
+        plan = build_plan(self.key, self.sigmas_host, self.eta, self.s_noise)
+        ns = self.noise_sampler
+        if ns is None and self.key == "dpmpp_sde":
+            ns = BrownianPairNoise(self.x.shape, self.x.device, self.x.dtype)
+        return run_plan(self.ldm_wrapper_model, self.x, plan, ns, self.fused), None
+
+
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=False):
     """util.py:46-60 ('uniform')."""
     if ddim_discr_method != 'uniform':

@@ -420,6 +420,51 @@ typedef struct {
 } crg_sampler_step_args;
 int crg_cfg_sampler_step(crg_ctx* ctx, void* stream, const crg_sampler_step_args* args);
 
+/* One fused evaluation step of the SD1.5 k-diffusion samplers the kinds above do not cover (k_diffusion sampling.py:195-252 DPM2 and
+ * DPM2 ancestral, :550-589 DPM++ SDE, :618-660 DPM++ 2M SDE, :663-710 DPM++ 3M SDE) with classifier-free guidance, in place, fp32, one
+ * rounding per operation in the reference's order.  Every kind first forms the guided denoised value of the evaluation's input xin (x,
+ * or x2 for DPM2_2) from the raw network output eps ([2][n], unconditional half first), as the kinds above do:
+ *   den_h = eps_h * c_out + xin,   den = den_u + cfg_scale * (den_c - den_u)      CompVisDenoiser (c_out = -sigma), CFG on denoised
+ * then, with z = noise (read only when add_noise):
+ *   DPM2_2   d2 = (x2 - den) / sigma;  x = x + d2 * dt  [+ (z * s_noise) * sigma_up]        sigma = sigma_mid, dt = target - sigma_i
+ *   SDE_1    x2 = m0 * x - m1 * den;  x2 = x2 + (z * s_noise) * sigma_up  (add_noise)       x is not written
+ *   SDE_2M   den_out = den;  last: x = den;  otherwise x = a * x + c1 * den,  have_old: x = x + c2 * (den - old[0]),
+ *            add_noise: x = x + ((z * p0) * p1) * s_noise
+ *   SDE_3M   den_out = den;  last: x = den;  otherwise x = a * x + c1 * den,
+ *            order 2: x = x + phi2 * ((den - old[0]) / r0)
+ *            order 3: d10 = (den - old[0]) / r0, d11 = (old[0] - old[1]) / r1, d1 = d10 + ((d10 - d11) * r0) / rsum,
+ *                     d2 = (d10 - d11) / rsum, x = (x + phi2 * d1) - phi3 * d2                      rsum = r0 + r1 in fp32
+ *            add_noise: as SDE_2M
+ * den_out may be a buffer the step does not read (the oldest of the history ring); it must not alias one it reads.  A buffer a kind
+ * or branch does not use is not dereferenced (old[] past what the order reads or on a last step, noise without add_noise, x2 and
+ * den_out of the kinds that have none). */
+enum { CRG_KSTEP_DPM2_2 = 0, CRG_KSTEP_SDE_1 = 1, CRG_KSTEP_SDE_2M = 2, CRG_KSTEP_SDE_3M = 3 };
+typedef struct {
+  int kind;                /* CRG_KSTEP_* */
+  int64_t n;               /* elements of x */
+  float* x;                /* [n] the sampler state: in / out (SDE_1: in) */
+  const float* eps;        /* [2][n] the network output of this evaluation */
+  float* x2;               /* [n] DPM2_2: in (xin); SDE_1: out (the second call's input) */
+  float* den_out;          /* [n] SDE_2M / SDE_3M: receives this step's denoised value */
+  const float* old[2];     /* SDE_2M: old[0] the previous denoised value (have_old); SDE_3M: old[0], old[1] the last two (order) */
+  const float* noise;      /* [n] z, read only when add_noise */
+  float c_out;             /* -sigma of the evaluation */
+  float cfg_scale;
+  float sigma;             /* DPM2_2: the divisor sigma_mid (> 0) */
+  float dt;                /* DPM2_2 */
+  float sigma_up, s_noise;
+  float m[2];              /* SDE_1: m0, m1 */
+  float a, c1, c2;         /* SDE_2M / SDE_3M: the exponential integrator's scalars; c2: SDE_2M's midpoint correction */
+  float p[2];              /* SDE_2M / SDE_3M noise: p0 = next sigma, p1 = sqrt(-expm1(-2 * eta * h)) */
+  float r[2], rsum;        /* SDE_3M: r0, r1 and r0 + r1 */
+  float phi2, phi3;        /* SDE_3M */
+  int order;               /* SDE_3M: 1..3 */
+  int last;                /* SDE_2M / SDE_3M: the next sigma is 0, x = den */
+  int have_old;            /* SDE_2M */
+  int add_noise;
+} crg_kstep_args;
+int crg_cfg_kstep(crg_ctx* ctx, void* stream, const crg_kstep_args* args);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
