@@ -164,6 +164,8 @@ SIGNATURES = {
                                      c_float, c_int]),
     "crg_cfg_sampler_step": (c_int, [c_void_p, c_void_p, C.POINTER(SamplerStepArgs)]),
     "crg_cfg_kstep": (c_int, [c_void_p, c_void_p, C.POINTER(KStepArgs)]),
+    "crg_resize_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_float, c_float, c_float]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

@@ -843,6 +843,53 @@ extern "C" int crg_cfg_kstep(crg_ctx* ctx, void* stream, const crg_kstep_args* a
   return 0;
 }
 
+namespace {
+// Bilinear upscale (align_corners = False) of NCHW fp32 planes fused with the forward diffusion of the result (see include/crg_hip.h).
+// The source rows / columns and their weights come from host-built tables (ATen's area_pixel_compute_source_index arithmetic in fp32);
+// the blend is horizontal, then vertical, and everything after it one fp32 rounding per operation (no FMA contraction).  Table indices
+// are clamped to the source plane, so a wrong table gives wrong values, never an out-of-bounds read.
+__global__ __launch_bounds__(256) void resize_noise_kernel(const float* __restrict__ x, const float* __restrict__ noise,
+                                                           float* __restrict__ out, long n, int h, int w, int H, int W,
+                                                           const int* __restrict__ yi, const float* __restrict__ yw,
+                                                           const int* __restrict__ xi, const float* __restrict__ xw, float a, float s,
+                                                           float d) {
+#pragma clang fp contract(off)
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int ox = (int)(i % W);
+    const long r = i / W;
+    const int oy = (int)(r % H);
+    const long plane = r / H;
+    const int y0 = min(max(yi[oy], 0), h - 1), y1 = min(max(yi[H + oy], 0), h - 1);
+    const int x0 = min(max(xi[ox], 0), w - 1), x1 = min(max(xi[W + ox], 0), w - 1);
+    const float wy0 = yw[oy], wy1 = yw[H + oy], wx0 = xw[ox], wx1 = xw[W + ox];
+    const float* p = x + plane * ((long)h * w);
+    const float top = wx0 * p[(long)y0 * w + x0] + wx1 * p[(long)y0 * w + x1];
+    const float bot = wx0 * p[(long)y1 * w + x0] + wx1 * p[(long)y1 * w + x1];
+    float v = a * (wy0 * top + wy1 * bot);
+    if (noise) v = v + s * noise[i];
+    out[i] = v / d;
+  }
+}
+}  // namespace
+
+extern "C" int crg_resize_noise(crg_ctx* ctx, void* stream, const void* x, const void* noise, void* out, int64_t planes, int h, int w,
+                                int H, int W, const int* y_idx, const float* y_wt, const int* x_idx, const float* x_wt, float a, float s,
+                                float d) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, x && out && y_idx && y_wt && x_idx && x_wt, "resize_noise: null pointer");
+  CRG_REQUIRE(ctx, x != out && noise != out, "resize_noise: out must not alias x or noise");
+  CRG_REQUIRE(ctx, planes > 0 && h > 0 && w > 0 && H > 0 && W > 0, "resize_noise: empty shape (%lld planes, %dx%d -> %dx%d)",
+              (long long)planes, h, w, H, W);
+  CRG_REQUIRE(ctx, d != 0.f, "resize_noise: the divisor must not be 0");
+  const int64_t n = planes * H * W;
+  hipStream_t st = (hipStream_t)stream;
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, 11.0 * n, 4.0 * (n * (noise ? 2 : 1) + planes * h * w));
+  hipLaunchKernelGGL(resize_noise_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const float*)x, (const float*)noise, (float*)out, (long)n, h,
+                     w, H, W, y_idx, y_wt, x_idx, x_wt, a, s, d);
+  CRG_CHECK_LAUNCH(ctx, "resize_noise");
+  return 0;
+}
+
 extern "C" int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, n > 0, "axpby: empty");

@@ -174,40 +174,103 @@ def txt2img(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tensor], *
     return (decode_images(ldm, samples) if decode else None), samples
 
 
+UPSCALERS = ("latent", "lanczos")  # Cremage's hires-fix upscalers (opt.hires_fix_upscaler), lower-cased
+
+
+def _upscaler(name: str) -> str:
+    key = str(name).lower()
+    if key not in UPSCALERS:
+        raise ValueError(f"unknown hires-fix upscaler {name!r} (one of {list(UPSCALERS)})")
+    return key
+
+
+def _control_cond(c, uc, hint):
+    """The two dict conditionings of a ControlNet run, holding the SAME hint object (image_generator.py:839-846, guess_mode False), so
+    that the doubled c_concat gets the CFG mark (samplers.cat_cond_dict)."""
+    return {"c_crossattn": [c], "c_concat": [hint]}, ({"c_crossattn": [uc], "c_concat": [hint]} if uc is not None else None)
+
+
+def upscale_encode_latents(smp, base: torch.Tensor, factor: float, t_enc: int, steps: int, fwd_noise: Optional[torch.Tensor] = None,
+                           fused: Optional[bool] = None) -> torch.Tensor:
+    """The latent upscaler's F.interpolate(bilinear) + k-diffusion stochastic_encode (image_generator.py:894, :975 and
+    k_diffusion_samplers.py:255-296).  `fused` (None: fp32 device latents): ONE launch, ops.upscale_noise with the host-computed
+    sqrt(acp_t) and sqrt(1 - acp_t) of smp.encode_scalars; otherwise the two torch calls.  The noise is `fwd_noise`, or randn of
+    the upscaled shape."""
+    import torch.nn.functional as F
+    b = base.shape[0]
+    if fused is None:
+        fused = base.is_cuda and base.dtype == torch.float32
+    if not fused:
+        up = F.interpolate(base, scale_factor=factor, mode="bilinear", align_corners=False)
+        return smp.stochastic_encode(up, torch.tensor([t_enc] * b, device=up.device), sampling_steps=steps, noise=fwd_noise)
+    if fwd_noise is None:
+        fwd_noise = torch.randn((b, base.shape[1], ops.upscaled_size(base.shape[2], factor), ops.upscaled_size(base.shape[3], factor)),
+                                device=base.device)
+    a, s = smp.encode_scalars(t_enc, steps)
+    return ops.upscale_noise(base.contiguous(), factor, fwd_noise.contiguous(), a, s, 1.0)
+
+
 @torch.no_grad()
 def txt2img_hires(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 20, sampler: str = "euler_a",
                   cfg_scale: float = 7.5, height: int = 512, width: int = 512, factor: float = 2.0, strength: float = 0.5,
                   x0: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, noise_sampler: Optional[Callable] = None,
-                  decode: bool = True):
-    """Hires-fix with the latent upscaler (image_generator.py:958-999): txt2img at (height, width); bilinear upscale of the final
-    latents by `factor`; forward-diffuse to t_enc = int(strength * steps) (k_diffusion_samplers.py:255-296) and denoise the last
-    t_enc + 1 sigmas at the larger size (img2img_sampling :227-246).  `sampler`: a SAMPLERS key or Cremage's menu name.  Returns
-    (images, latents, base latents)."""
-    import torch.nn.functional as F
+                  decode: bool = True, upscaler: str = "latent", hint: Optional[torch.Tensor] = None,
+                  hint_hires: Optional[torch.Tensor] = None, enc_noise: Optional[torch.Tensor] = None):
+    """Hires-fix (image_generator.py:889-932, :958-999, :1020-1098): txt2img at (height, width), an upscale by `factor`, forward
+    diffusion to t_enc = int(strength * steps) (k_diffusion_samplers.py:255-296) and a denoise of the last t_enc + 1 sigmas at the
+    larger size (img2img_sampling :192-211, :227-246).  `sampler`: a SAMPLERS key or Cremage's menu name, used by both passes.
+    `upscaler`:
+      "latent"  - bilinear F.interpolate of the final latents.  On a ControlNet run (`hint`) with fp32 device latents the upscale and
+                  the forward diffusion are ONE launch (ops.upscale_noise).  Without `hint` the two torch calls stay: the launch rounds
+                  every operation once, ATen's device kernel contracts its blend into fused multiply-adds, so the results differ in
+                  the last bits and the existing fixtures of this route keep the arithmetic they were recorded against.
+      "lanczos" - decode, postprocess.upscale_uint8 (an APPROXIMATION of the reference's cv2.INTER_LANCZOS4, see there), * 2 - 1,
+                  encode (`enc_noise`: the posterior sample's noise), forward diffusion, second pass.
+    `hint` ([b,3,height,width] in [0,1], ControlLDM only): both passes run dict conditioning; the second pass uses `hint_hires`
+    ([b,3,height*factor,width*factor]), by default postprocess.upscale_uint8(hint) - the same approximation, of scale_control_image
+    (:552-562).  The ControlNet's one-entry hint cache then holds the second pass' guided hint.  Returns (images, latents, base
+    latents)."""
+    from . import postprocess as PP
+    upscaler = _upscaler(upscaler)
     b = c.shape[0]
     smp = _sampler(sampler)[1](ldm)
     smp.noise_sampler = noise_sampler
-    base, _ = smp.sample(S=steps, conditioning=c, batch_size=b, shape=[4, height // 8, width // 8], verbose=False,
-                         unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x0=x0)
-    up = F.interpolate(base, scale_factor=factor, mode="bilinear", align_corners=False)
+    cond, ucond = _control_cond(c, uc, hint) if hint is not None else (c, uc)
+    base, _ = smp.sample(S=steps, conditioning=cond, batch_size=b, shape=[4, height // 8, width // 8], verbose=False,
+                         unconditional_guidance_scale=cfg_scale, unconditional_conditioning=ucond, x0=x0)
     t_enc = int(strength * steps)
-    z_enc = smp.stochastic_encode(up, torch.tensor([t_enc] * b, device=up.device), sampling_steps=steps, noise=fwd_noise)
-    samples, _ = smp.sample(S=steps, conditioning=c, batch_size=b, shape=list(up.shape[1:]), verbose=False,
-                            unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc, x0=z_enc, denoising_steps=t_enc)
+    big_w, big_h = int(width * factor), int(height * factor)
+    if upscaler == "latent":
+        z_enc = upscale_encode_latents(smp, base, factor, t_enc, steps, fwd_noise, fused=None if hint is not None else False)
+    else:
+        scaled = PP.upscale_uint8(decode_images(ldm, base), big_w, big_h).contiguous() * 2.0 - 1.0
+        init_latent = ldm.get_first_stage_encoding(ldm.encode_first_stage(scaled), enc_noise)
+        z_enc = smp.stochastic_encode(init_latent, torch.tensor([t_enc] * b, device=init_latent.device), sampling_steps=steps,
+                                      noise=fwd_noise)
+    if hint is not None:
+        if hint_hires is None:
+            hint_hires = PP.upscale_uint8(hint, big_w, big_h).contiguous()
+        cond, ucond = _control_cond(c, uc, hint_hires)
+    samples, _ = smp.sample(S=steps, conditioning=cond, batch_size=b, shape=list(z_enc.shape[1:]), verbose=False,
+                            unconditional_guidance_scale=cfg_scale, unconditional_conditioning=ucond, x0=z_enc, denoising_steps=t_enc)
     return (decode_images(ldm, samples) if decode else None), samples, base
 
 
 @torch.no_grad()
 def img2img(ldm: LatentDiffusion, init_image: torch.Tensor, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 20,
             strength: float = 0.75, cfg_scale: float = 7.5, enc_noise: Optional[torch.Tensor] = None,
-            fwd_noise: Optional[torch.Tensor] = None, decode: bool = True):
-    """SD1.5 img2img as the reference drives it: sampler forced to DDIM (image_generator.py:679-681)."""
+            fwd_noise: Optional[torch.Tensor] = None, decode: bool = True, hint: Optional[torch.Tensor] = None):
+    """SD1.5 img2img as the reference drives it: sampler forced to DDIM (image_generator.py:679-681).  `hint` ([b,3,H,W] in [0,1],
+    ControlLDM only): ControlNet img2img (:850-875, img2img_sampling :168-190) - the two dict conditionings hold the same hint object
+    as txt2img builds them, and DDIMSampler.decode runs them through its fused step."""
     b = init_image.shape[0]
     init_latent = ldm.get_first_stage_encoding(ldm.encode_first_stage(init_image), enc_noise)
     t_enc = int(strength * steps)
     smp = DDIMSampler(ldm)
     smp.make_schedule(ddim_num_steps=steps, ddim_eta=0.0, verbose=False)
     z_enc = smp.stochastic_encode(init_latent, torch.tensor([t_enc] * b, device=init_latent.device), noise=fwd_noise)
+    if hint is not None:
+        c, uc = _control_cond(c, uc, hint)
     samples = smp.decode(z_enc, c, t_enc, unconditional_guidance_scale=cfg_scale, unconditional_conditioning=uc)
     return (decode_images(ldm, samples) if decode else None), samples
 
@@ -328,6 +391,42 @@ def img2img_sdxl(eng, init_image: torch.Tensor, c: dict, uc: dict, *, steps: int
         return None, samples
     x = eng.decode_first_stage(samples)
     return ops.affine_cast(x, 0.5, 0.5, torch.float32, 0.0, 1.0), samples
+
+
+@torch.no_grad()
+def txt2img_sdxl_hires(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
+                       factor: float = 2.0, strength: float = 0.3, upscaler: str = "latent", c_hires: Optional[dict] = None,
+                       uc_hires: Optional[dict] = None, x0: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None,
+                       enc_noise: Optional[torch.Tensor] = None, sampler: str = "euler_edm", discretization: str = "legacy_ddpm",
+                       sampler_options: Optional[dict] = None, decode: bool = True):
+    """SDXL hires-fix (sdxl_image_generator.py:166-230): txt2img at (height, width), then an img2img pass at `strength` on the result
+    upscaled by `factor` (run_img2img -> do_img2img, sdxl_image_generator_utils.py:986-1017, which adds noise).  `upscaler`:
+      "latent"  - bilinear F.interpolate of the base latents, no VAE in between (skip_encode): DiffusionEngine.img2img_latent, on
+                  fp32 device latents one launch for the upscale and the noising.
+      "lanczos" - decode, postprocess.upscale_uint8 (an APPROXIMATION of the reference's cv2.INTER_LANCZOS4, see there), then
+                  DiffusionEngine.img2img (encode with `enc_noise`, noise, sample).
+    `c_hires` / `uc_hires`: the conditioning of the second pass.  The reference rebuilds the `vector` conditioning there with the
+    upscaled size as original / target size (run_img2img :265-283); the conditioner is PyTorch and outside this package, so the caller
+    hands in what it gives.  None reuses c / uc - which DIFFERS from Cremage: the size embedding then still says (height, width).
+    The reference runs the second pass one image at a time with a fresh randn each; here the batch runs at once - the same arithmetic
+    per image - and `fwd_noise` ([b,4,H*factor/8,W*factor/8]) is the noise of the whole batch.  Both passes use `sampler`,
+    `discretization` and `sampler_options` (as in txt2img_sdxl).  Returns (images or None, latents, base latents)."""
+    from . import postprocess as PP
+    upscaler = _upscaler(upscaler)
+    c2, uc2 = (c if c_hires is None else c_hires), (uc if uc_hires is None else uc_hires)
+    smp = dict(sampler=sampler, discretization=discretization, options=sampler_options)
+    first, base = txt2img_sdxl(eng, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0,
+                               decode=upscaler == "lanczos", sampler=sampler, discretization=discretization,
+                               sampler_options=sampler_options)
+    if upscaler == "latent":
+        samples = eng.img2img_latent(base, c2, uc2, steps, strength, cfg_scale, fwd_noise=fwd_noise, factor=factor, **smp)
+    else:
+        scaled = PP.upscale_uint8(first, int(width * factor), int(height * factor)).contiguous() * 2.0 - 1.0
+        samples = eng.img2img(scaled, c2, uc2, steps, strength, cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise, **smp)
+    if not decode:
+        return None, samples, base
+    x = eng.decode_first_stage(samples)
+    return ops.affine_cast(x, 0.5, 0.5, torch.float32, 0.0, 1.0), samples, base
 
 
 @torch.no_grad()

@@ -371,12 +371,24 @@ class KDiffusionSamplerBase(object):
     def compute_sigmas_host(self, n: int):
         """The same schedule computed on the CPU from a cached CPU copy of alphas_cumprod (fp32, the arithmetic of the
         reference run on a CPU device): steers the sampling loop without touching the device (see _host_sigmas)."""
+        acp = self._acp_host()
+        sched = DiscreteSchedule(((1 - acp) / acp) ** 0.5, False)
+        return sched.get_sigmas(n)
+
+    def _acp_host(self):
+        """The model's alphas_cumprod as a CPU fp32 tensor, copied once per version of the buffer."""
         m = self.ldm_model
         acp = m.__dict__.get("_crg_acp_cpu")
         if acp is None or acp[0] != m.alphas_cumprod._version:
             acp = m.__dict__["_crg_acp_cpu"] = (m.alphas_cumprod._version, m.alphas_cumprod.detach().float().cpu())
-        sched = DiscreteSchedule(((1 - acp[1]) / acp[1]) ** 0.5, False)
-        return sched.get_sigmas(n)
+        return acp[1]
+
+    def encode_scalars(self, t_enc: int, sampling_steps: int):
+        """(sqrt(acp_t), sqrt(1 - acp_t)) of stochastic_encode(x0, [t_enc] * b, sampling_steps) as Python floats, from the CPU copy of
+        the table with stochastic_encode's own fp32 arithmetic - for ops.upscale_noise, without touching the device."""
+        t = int((torch.tensor([t_enc]) * 1000.0 / sampling_steps).long())
+        acp = self._acp_host()[t]
+        return float(acp.sqrt()), float((1. - acp).sqrt())
 
     @torch.no_grad()
     def _sample_common_prep(self, S, batch_size, shape, conditioning=None, x0=None, unconditional_guidance_scale=1.,
@@ -1031,14 +1043,37 @@ class DDIMSampler(object):
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None):
+        """ddim.py:657-676: the last `t_start` steps of the schedule of make_schedule, from x_latent (not mutated).  `cond` /
+        `unconditional_conditioning` are tensors, or dicts ({"c_crossattn": [...], "c_concat": [hint]}, the ControlNet img2img of
+        image_generator.py:168-190): dicts are doubled once through _cat_cond - a c_concat entry that is ONE object in both dicts gets
+        the CFG mark, as in `sample` - and, with CFG on fp32 device latents and no callback, run `sample`'s fused executor: hoisted time
+        rows, one doubled-input copy and crg_cfg_ddim_step with the step scalars of make_schedule.  Tensor conditioning keeps the
+        elementwise chain of p_sample_ddim op for op (tests/golden/traj_ddim_img2img pins it); moving that route to the fused step is
+        a separate change."""
         assert not use_original_steps
         timesteps = self.ddim_timesteps[:t_start]
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        guided = uc is not None and scale != 1.
         # one concatenated conditioning for the whole decode (K/V cache friendly); same values as ddim.py:553
         self._c_in = None
-        if unconditional_conditioning is not None and unconditional_guidance_scale != 1. and torch.is_tensor(cond):
-            self._c_in = torch.cat([unconditional_conditioning, cond])
+        if guided:
+            self._c_in = self._cat_cond(cond, uc) if isinstance(cond, dict) else torch.cat([uc, cond])
+        if guided and isinstance(cond, dict) and callback is None and x_latent.is_cuda and x_latent.dtype == torch.float32:
+            from . import ops
+            x, b = x_latent.clone().contiguous(), x_latent.shape[0]  # updated in place by the fused step
+            t_rep = torch.tensor(time_range.copy(), dtype=torch.long).reshape(-1, 1).expand(-1, 2 * b).contiguous().to(x.device)
+            t_rows = self._time_rows(t_rep)
+            for i in range(total_steps):
+                sc = self._step_scalars[total_steps - i - 1]
+                z = torch.randn_like(x) if sc[4] != 0. else None  # noise_like of a schedule made with eta > 0 (ddim.py:603)
+                xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+                xx.copy_(x.unsqueeze(0).expand_as(xx))  # cat([x] * 2) as one copy
+                e2 = self.model.apply_model(_mark_dup(xx.view((2 * b,) + tuple(x.shape[1:]))), t_rows[i], self._c_in)
+                ops.cfg_ddim_step_(x, e2.contiguous(), z, scale, *sc)
+            self._c_in = None
+            return x
         x_dec = x_latent
         for i, step in enumerate(time_range):
             index = total_steps - i - 1

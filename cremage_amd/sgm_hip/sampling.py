@@ -741,6 +741,32 @@ class DiffusionEngine(nn.Module):
         return self.run_sampler(smp, noised_z, cond, uc)
 
     @torch.no_grad()
+    def img2img_latent(self, z, cond: Dict, uc: Dict, steps: int, strength: float, cfg_scale: float, fwd_noise=None, factor: float = 1.0,
+                       sampler: str = "euler_edm", discretization: str = "legacy_ddpm", options: Optional[Dict] = None):
+        """do_img2img with skip_encode and add_noise (sdxl_image_generator_utils.py:986-1017) on latents z upscaled by `factor`
+        (bilinear, align_corners False: the latent upscaler of the SDXL hires-fix, sdxl_image_generator.py:196-199): noise to
+        sigma_0 of the Img2Img-pruned schedule, divide by sqrt(1 + sigma_0^2), sample over the remaining sigmas.  On fp32 device
+        latents the upscale and the noising are ONE launch (ops.upscale_noise with host scalars); otherwise the torch expression
+        of `img2img`.  `fwd_noise`: the noise, of the upscaled shape (randn by default)."""
+        smp = self.make_sampler(sampler, steps, cfg_scale, z.device, img2img_strength=strength, discretization=discretization,
+                                options=options)
+        if z.is_cuda and z.dtype == torch.float32:
+            from .. import ops
+            s0 = smp.discretization(steps)[0]  # CPU fp32, the arithmetic of the device expression below
+            if fwd_noise is None:
+                fwd_noise = torch.randn((z.shape[0], z.shape[1], ops.upscaled_size(z.shape[2], factor),
+                                         ops.upscaled_size(z.shape[3], factor)), device=z.device)
+            noised_z = ops.upscale_noise(z.contiguous(), factor, fwd_noise.contiguous(), 1.0, float(s0),
+                                         float(torch.sqrt(1.0 + s0 ** 2.0)))
+        else:
+            if factor != 1.0:
+                z = torch.nn.functional.interpolate(z, scale_factor=factor, mode="bilinear", align_corners=False)
+            sigmas = smp.discretization(steps, device=z.device)
+            noise = torch.randn_like(z) if fwd_noise is None else fwd_noise
+            noised_z = (z + noise * sigmas[0]) / torch.sqrt(1.0 + sigmas[0] ** 2.0)
+        return self.run_sampler(smp, noised_z, cond, uc)
+
+    @torch.no_grad()
     def sample(self, x, cond: Dict, uc: Dict, steps: int, cfg_scale: float, sampler: str = "euler_edm",
                stage2strength: Optional[float] = None, discretization: str = "legacy_ddpm", options: Optional[Dict] = None):
         """do_sample, sdxl_image_generator_utils.py:695-707: sampler(denoiser, randn, cond=c, uc=uc).  `stage2strength`: the base

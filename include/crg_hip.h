@@ -465,6 +465,17 @@ typedef struct {
 } crg_kstep_args;
 int crg_cfg_kstep(crg_ctx* ctx, void* stream, const crg_kstep_args* args);
 
+/* Hires-fix "upscale the latents and forward-diffuse them" as one launch, fp32 NCHW, x [planes][h][w] -> out [planes][H][W]:
+ *   up  = bilinear(x), align_corners = False        F.interpolate(scale_factor), image_generator.py:894,975; sdxl_image_generator.py:198
+ *   out = (a * up [+ s * noise]) / d                one fp32 rounding per operation, in this order, no contraction
+ * noise [planes][H][W] may be NULL (no noise term); x and noise are only read.  DDIM and k-diffusion stochastic_encode: a = sqrt(acp_t),
+ * s = sqrt(1 - acp_t), d = 1; SDXL do_img2img: a = 1, s = sigma_0, d = sqrt(1 + sigma_0^2).
+ * The source rows and their weights are host-built DEVICE tables, ATen's arithmetic in fp32: y_idx int32 [2][H] (row i0, then row i1 of
+ * every output row), y_wt fp32 [2][H] (w0, then w1); x_idx / x_wt the same for the W columns.  up = w0y * (w0x * x[i0y][i0x] + w1x *
+ * x[i0y][i1x]) + w1y * (the same on row i1y).  Indices are clamped to the source plane. */
+int crg_resize_noise(crg_ctx* ctx, void* stream, const void* x, const void* noise, void* out, int64_t planes, int h, int w, int H, int W,
+                     const int* y_idx, const float* y_wt, const int* x_idx, const float* x_wt, float a, float s, float d);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
