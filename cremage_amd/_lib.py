@@ -109,6 +109,25 @@ class KStepArgs(C.Structure):
     ]
 
 
+class ResampleArgs(C.Structure):
+    _fields_ = [
+        ("src", c_void_p), ("src_u8", c_int),
+        ("src_sn", c_int64), ("src_sc", c_int64), ("src_sy", c_int64), ("src_sx", c_int64),
+        ("src_h", c_int), ("src_w", c_int),
+        ("x0", c_int), ("y0", c_int), ("w", c_int), ("h", c_int),
+        ("N", c_int), ("C", c_int),
+        ("W", c_int), ("H", c_int),
+        ("kx", c_void_p), ("x_bounds", c_void_p), ("ksize_x", c_int),
+        ("ky", c_void_p), ("y_bounds", c_void_p), ("ksize_y", c_int),
+        ("dst", c_void_p), ("dst_u8", c_int),
+        ("dst_sn", c_int64), ("dst_sc", c_int64), ("dst_sy", c_int64), ("dst_sx", c_int64),
+        ("dst_h", c_int), ("dst_w", c_int),
+        ("ox", c_int), ("oy", c_int),
+        ("out_a", c_float), ("out_b", c_float),
+        ("fill", c_int), ("fill_value", c_float),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -166,6 +185,7 @@ SIGNATURES = {
     "crg_cfg_kstep": (c_int, [c_void_p, c_void_p, C.POINTER(KStepArgs)]),
     "crg_resize_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_float, c_float, c_float]),
+    "crg_resample_u8": (c_int, [c_void_p, c_void_p, C.POINTER(ResampleArgs)]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

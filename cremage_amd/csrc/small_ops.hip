@@ -890,6 +890,186 @@ extern "C" int crg_resize_noise(crg_ctx* ctx, void* stream, const void* x, const
   return 0;
 }
 
+namespace {
+// PIL's 8-bit two-pass resize of a window (see include/crg_hip.h).  One block per 64 x 32 output tile of one (image, channel) plane.
+// The source rows the tile's vertical taps read are walked in chunks of RS_CH rows: the horizontal pass of a chunk goes to LDS as
+// uint8 (PIL clips between the passes), then every thread adds the chunk's share of the vertical taps of its 4 x 2 output pixels to
+// integer accumulators in registers - so ksize is a run-time value and LDS is 2 KiB whatever the scale.  A thread's four pixels of a
+// row are consecutive columns: one 32-bit LDS read per vertical tap, one 16-byte (fp32) or 4-byte (uint8) store per row.
+constexpr int RS_TX = 64, RS_TY = 32, RS_CH = 32, RS_BITS = 22;
+
+template <bool U8>
+__device__ __forceinline__ int rs_load(const void* p, long off) {
+  if (U8) return ((const unsigned char*)p)[off];
+  const float s = fminf(fmaxf(((const float*)p)[off], 0.f), 1.f);
+  return (int)(255.0f * s);
+}
+__device__ __forceinline__ int rs_clip8(int acc) { return min(max(acc >> RS_BITS, 0), 255); }
+
+template <bool SU8, bool DU8>
+__global__ __launch_bounds__(256) void resample_u8_kernel(const crg_resample_args a) {
+#pragma clang fp contract(off)
+  __shared__ unsigned int t_lds[RS_CH * (RS_TX / 4)];
+  unsigned char* t8 = reinterpret_cast<unsigned char*>(t_lds);
+  const int tid = threadIdx.x;
+  const int X0 = blockIdx.x * RS_TX, Y0 = blockIdx.y * RS_TY;
+  const int n = blockIdx.z / a.C, c = blockIdx.z % a.C;
+  const long sbase = n * a.src_sn + c * a.src_sc + a.y0 * a.src_sy + a.x0 * a.src_sx;
+  // the tile's source rows [rlo, rhi): first row's ymin .. last row's ymin + count (bounds do not decrease)
+  const int Yl = min(Y0 + RS_TY, a.H) - 1;
+  const int rlo = min(max(a.y_bounds[2 * Y0], 0), a.h);
+  int rhi = min(max(a.y_bounds[2 * Yl], 0), a.h);
+  rhi += min(max(a.y_bounds[2 * Yl + 1], 0), min(a.ksize_y, a.h - rhi));
+  // horizontal pass: column hc of rows hr, hr + 4, ...
+  const int hc = tid & (RS_TX - 1), hr = tid >> 6;
+  const int hX = min(X0 + hc, a.W - 1);
+  const int hxmin = min(max(a.x_bounds[2 * hX], 0), a.w);
+  const int hxcnt = min(max(a.x_bounds[2 * hX + 1], 0), min(a.ksize_x, a.w - hxmin));
+  const int* hk = a.kx + (long)hX * a.ksize_x;
+  // vertical pass: columns vx .. vx + 3 of rows Y0 + vy and Y0 + vy + 16
+  const int vq = tid & 15, vy = tid >> 4;
+  int vmin[2], vend[2], acc[2][4];
+  const int* vk[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int Y = min(Y0 + vy + 16 * r, a.H - 1);
+    vmin[r] = min(max(a.y_bounds[2 * Y], 0), a.h);
+    vend[r] = vmin[r] + min(max(a.y_bounds[2 * Y + 1], 0), min(a.ksize_y, a.h - vmin[r]));
+    vk[r] = a.ky + (long)Y * a.ksize_y - vmin[r];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[r][e] = 1 << (RS_BITS - 1);
+  }
+  for (int cs = rlo; cs < rhi; cs += RS_CH) {
+    int h[RS_CH / 4];
+    long roff[RS_CH / 4];
+#pragma unroll
+    for (int i = 0; i < RS_CH / 4; ++i) {
+      h[i] = 1 << (RS_BITS - 1);
+      roff[i] = sbase + (long)min(cs + hr + 4 * i, rhi - 1) * a.src_sy + (long)hxmin * a.src_sx;  // rows past rhi: computed, never read
+    }
+    for (int j = 0; j < hxcnt; ++j) {
+      const int k = hk[j];
+#pragma unroll
+      for (int i = 0; i < RS_CH / 4; ++i) h[i] += rs_load<SU8>(a.src, roff[i] + j * a.src_sx) * k;
+    }
+#pragma unroll
+    for (int i = 0; i < RS_CH / 4; ++i) t8[(hr + 4 * i) * RS_TX + hc] = (unsigned char)rs_clip8(h[i]);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int lo = max(vmin[r], cs), hi = min(vend[r], min(cs + RS_CH, rhi));
+      for (int j = lo; j < hi; ++j) {
+        const int k = vk[r][j];
+        const unsigned int u = t_lds[(j - cs) * (RS_TX / 4) + vq];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[r][e] += (int)((u >> (8 * e)) & 255u) * k;
+      }
+    }
+    __syncthreads();
+  }
+  const int X = X0 + 4 * vq;
+  if (X >= a.W) return;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int Y = Y0 + vy + 16 * r;
+    if (Y >= a.H) continue;
+    const long doff = n * a.dst_sn + c * a.dst_sc + (long)(a.oy + Y) * a.dst_sy + (long)(a.ox + X) * a.dst_sx;
+    int v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = rs_clip8(acc[r][e]);
+    const bool row4 = X + 3 < a.W && a.dst_sx == 1;
+    if (DU8) {
+      unsigned char* d = (unsigned char*)a.dst + doff;
+      if (row4 && ((uintptr_t)d & 3) == 0) {
+        *reinterpret_cast<unsigned int*>(d) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
+      } else {
+        for (int e = 0; e < 4 && X + e < a.W; ++e) d[e * a.dst_sx] = (unsigned char)v[e];
+      }
+    } else {
+      float* d = (float*)a.dst + doff;
+      float f[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float u = (float)v[e] / 255.0f;
+        f[e] = a.out_a * u + a.out_b;
+      }
+      if (row4 && ((uintptr_t)d & 15) == 0) {
+        *reinterpret_cast<f32x4*>(d) = f32x4{f[0], f[1], f[2], f[3]};
+      } else {
+        for (int e = 0; e < 4 && X + e < a.W; ++e) d[e * a.dst_sx] = f[e];
+      }
+    }
+  }
+}
+
+// every destination pixel outside the result's rectangle <- the fill value (the two launches write disjoint pixels)
+template <bool DU8>
+__global__ __launch_bounds__(256) void resample_fill_kernel(const crg_resample_args a, long total) {
+  const unsigned char fb = (unsigned char)min(max((int)a.fill_value, 0), 255);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int x = (int)(i % a.dst_w);
+    const long r = i / a.dst_w;
+    const int y = (int)(r % a.dst_h);
+    const long plane = r / a.dst_h;
+    if (x >= a.ox && x < a.ox + a.W && y >= a.oy && y < a.oy + a.H) continue;
+    const long doff = (plane / a.C) * a.dst_sn + (plane % a.C) * a.dst_sc + (long)y * a.dst_sy + (long)x * a.dst_sx;
+    if (DU8) ((unsigned char*)a.dst)[doff] = fb;
+    else ((float*)a.dst)[doff] = a.fill_value;
+  }
+}
+}  // namespace
+
+extern "C" int crg_resample_u8(crg_ctx* ctx, void* stream, const crg_resample_args* args) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, args != nullptr, "resample_u8: null args");
+  const crg_resample_args& a = *args;
+  CRG_REQUIRE(ctx, a.src && a.dst, "resample_u8: null source or destination");
+  CRG_REQUIRE(ctx, a.kx && a.x_bounds && a.ky && a.y_bounds, "resample_u8: null coefficient or bounds table");
+  CRG_REQUIRE(ctx, (a.src_u8 == 0 || a.src_u8 == 1) && (a.dst_u8 == 0 || a.dst_u8 == 1), "resample_u8: src_u8 / dst_u8 must be 0 or 1 (got %d, %d)",
+              a.src_u8, a.dst_u8);
+  CRG_REQUIRE(ctx, a.N > 0 && a.C > 0 && (int64_t)a.N * a.C <= 65535, "resample_u8: N * C = %d * %d must be in 1..65535", a.N, a.C);
+  CRG_REQUIRE(ctx, a.src_h > 0 && a.src_w > 0 && a.dst_h > 0 && a.dst_w > 0, "resample_u8: empty image (source %dx%d, destination %dx%d)",
+              a.src_h, a.src_w, a.dst_h, a.dst_w);
+  CRG_REQUIRE(ctx, a.w > 0 && a.h > 0 && a.x0 >= 0 && a.y0 >= 0 && a.x0 <= a.src_w - a.w && a.y0 <= a.src_h - a.h,
+              "resample_u8: window (x %d, y %d, w %d, h %d) is empty or outside the %dx%d source", a.x0, a.y0, a.w, a.h, a.src_h, a.src_w);
+  CRG_REQUIRE(ctx, a.W > 0 && a.H > 0 && a.ox >= 0 && a.oy >= 0 && a.ox <= a.dst_w - a.W && a.oy <= a.dst_h - a.H,
+              "resample_u8: result %dx%d at (x %d, y %d) is empty or outside the %dx%d destination", a.H, a.W, a.ox, a.oy, a.dst_h, a.dst_w);
+  CRG_REQUIRE(ctx, a.W <= 65535 * RS_TX && a.H <= 65535 * RS_TY, "resample_u8: result %dx%d is too large", a.H, a.W);
+  CRG_REQUIRE(ctx, a.ksize_x > 0 && a.ksize_y > 0, "resample_u8: ksize must be positive (got %d, %d)", a.ksize_x, a.ksize_y);
+  CRG_REQUIRE(ctx, a.src_sx > 0 && a.src_sy > 0 && a.src_sn >= 0 && a.src_sc >= 0, "resample_u8: source strides must be positive (n and c: not negative)");
+  CRG_REQUIRE(ctx, a.dst_sx > 0 && a.dst_sy > 0 && (a.dst_sn > 0 || a.N == 1) && a.dst_sn >= 0 && (a.dst_sc > 0 || a.C == 1) && a.dst_sc >= 0,
+              "resample_u8: destination strides must be positive");
+  CRG_REQUIRE(ctx, a.dst_u8 || (a.out_a == a.out_a && a.out_b == a.out_b), "resample_u8: out_a / out_b is NaN");
+  CRG_REQUIRE(ctx, !a.fill || a.fill_value == a.fill_value, "resample_u8: the fill value is NaN");
+  CRG_REQUIRE(ctx, !a.fill || !a.dst_u8 || (a.fill_value >= 0.f && a.fill_value <= 255.f), "resample_u8: the fill of an uint8 destination must be in 0..255 (got %g)",
+              (double)a.fill_value);
+  // byte intervals the launch reads (the window) and writes (the rectangle, or with fill the whole destination)
+  const int64_t se = a.src_u8 ? 1 : 4, de = a.dst_u8 ? 1 : 4;
+  const char* s0 = (const char*)a.src + se * (a.y0 * a.src_sy + a.x0 * a.src_sx);
+  const char* s1 = s0 + se * ((a.N - 1) * a.src_sn + (a.C - 1) * a.src_sc + (a.h - 1) * a.src_sy + (a.w - 1) * a.src_sx + 1);
+  const int dy = a.fill ? 0 : a.oy, dx = a.fill ? 0 : a.ox, dh = a.fill ? a.dst_h : a.H, dw = a.fill ? a.dst_w : a.W;
+  const char* d0 = (const char*)a.dst + de * (dy * a.dst_sy + dx * a.dst_sx);
+  const char* d1 = d0 + de * ((a.N - 1) * a.dst_sn + (a.C - 1) * a.dst_sc + (dh - 1) * a.dst_sy + (dw - 1) * a.dst_sx + 1);
+  CRG_REQUIRE(ctx, s1 <= d0 || d1 <= s0, "resample_u8: source and destination overlap");
+  hipStream_t st = (hipStream_t)stream;
+  const double planes = (double)a.N * a.C, px = planes * a.H * a.W;
+  crg_prof_scope ps(ctx, st, CRG_K_ELEMENTWISE, 2.0 * px * (a.ksize_x * 0.5 + a.ksize_y),
+                    planes * ((double)se * a.h * a.w + (double)de * (a.fill ? (double)a.dst_h * a.dst_w : (double)a.H * a.W)));
+  const dim3 grid((a.W + RS_TX - 1) / RS_TX, (a.H + RS_TY - 1) / RS_TY, a.N * a.C);
+  if (a.src_u8 && a.dst_u8) hipLaunchKernelGGL((resample_u8_kernel<true, true>), grid, dim3(256), 0, st, a);
+  else if (a.src_u8) hipLaunchKernelGGL((resample_u8_kernel<true, false>), grid, dim3(256), 0, st, a);
+  else if (a.dst_u8) hipLaunchKernelGGL((resample_u8_kernel<false, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((resample_u8_kernel<false, false>), grid, dim3(256), 0, st, a);
+  CRG_CHECK_LAUNCH(ctx, "resample_u8");
+  if (a.fill && (a.W < a.dst_w || a.H < a.dst_h)) {
+    const long total = (long)a.N * a.C * a.dst_h * a.dst_w;
+    if (a.dst_u8) hipLaunchKernelGGL(resample_fill_kernel<true>, dim3(grid_for(total)), dim3(256), 0, st, a, total);
+    else hipLaunchKernelGGL(resample_fill_kernel<false>, dim3(grid_for(total)), dim3(256), 0, st, a, total);
+    CRG_CHECK_LAUNCH(ctx, "resample_u8 (fill)");
+  }
+  return 0;
+}
+
 extern "C" int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype) {
   if (!ctx) return -22;
   CRG_REQUIRE(ctx, n > 0, "axpby: empty");

@@ -1277,6 +1277,121 @@ def upscale_noise(x: torch.Tensor, factor: float, noise: Optional[torch.Tensor] 
     return _written(out)
 
 
+# ---------------------------------------------------------------------------------- pixel-space Lanczos resize (PIL's, 8-bit)
+RESAMPLE_BITS = 22  # Resample.c PRECISION_BITS = 32 - 8 - 2
+
+
+def _lanczos3(x: float) -> float:
+    """Resample.c lanczos_filter / sinc_filter, in double."""
+    if -3.0 <= x < 3.0:
+        def sinc(v):
+            if v == 0.0:
+                return 1.0
+            v = v * math.pi
+            return math.sin(v) / v
+        return sinc(x) * sinc(x / 3.0)
+    return 0.0
+
+
+@functools.lru_cache(maxsize=64)
+def lanczos_tables(in_size: int, out_size: int):
+    """(ksize, bounds, coeffs) of PIL's 8-bit Lanczos resize of `in_size` samples to `out_size` (Resample.c precompute_coeffs +
+    normalize_coeffs_8bpc, double arithmetic): scale = in / out, support = 3 * max(scale, 1), ksize = ceil(support) * 2 + 1; per output
+    xx: center = (xx + 0.5) * scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in), weights
+    lanczos((x + xmin - center + 0.5) / max(scale, 1)) normalised by their sum, then int(k * 2^22 +- 0.5) (towards zero, as C's cast).
+    bounds: ((xmin, count), ...) per output, coeffs: `ksize` ints per output (zero past count).  PIL skips a pass whose lengths are
+    equal; for in_size == out_size this returns the one-tap table {2^22} with bounds (i, 1), which gives clip8((2^21 + q * 2^22) >> 22)
+    = q.  Cached per (in_size, out_size); tuples, so the cached value cannot be written."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"lanczos_tables: sizes must be positive (got {in_size} -> {out_size})")
+    one = 1 << RESAMPLE_BITS
+    if in_size == out_size:
+        return 1, tuple((i, 1) for i in range(out_size)), tuple((one,) for _ in range(out_size))
+    scale = float(in_size) / float(out_size)
+    filterscale = max(scale, 1.0)
+    support = 3.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    bounds, coeffs = [], []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        k = [_lanczos3((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for w in k:
+            ww += w
+        if ww != 0.0:
+            k = [w / ww for w in k]
+        k = [int(-0.5 + w * one) if w < 0 else int(0.5 + w * one) for w in k]
+        bounds.append((xmin, xmax))
+        coeffs.append(tuple(k + [0] * (ksize - xmax)))
+    return ksize, tuple(bounds), tuple(coeffs)
+
+
+_LANCZOS_TABLES = {}  # (in_size, out_size, device) -> (ksize, int32 [out][ksize], int32 [out][2]) on the device: uploaded once
+
+
+def _lanczos_device_tables(in_size: int, out_size: int, device):
+    key = (int(in_size), int(out_size), device)
+    t = _LANCZOS_TABLES.get(key)
+    if t is None:
+        ksize, bounds, coeffs = lanczos_tables(in_size, out_size)
+        t = _LANCZOS_TABLES[key] = (ksize, torch.tensor(coeffs, dtype=torch.int32).to(device), torch.tensor(bounds, dtype=torch.int32).to(device))
+    return t
+
+
+def resample_u8(src: torch.Tensor, size: Tuple[int, int], window: Optional[Tuple[int, int, int, int]] = None,
+                out: Optional[torch.Tensor] = None, out_offset: Tuple[int, int] = (0, 0), out_affine: Tuple[float, float] = (1.0, 0.0),
+                fill: Optional[float] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """PIL's `crop(window).resize(size, Image.LANCZOS)` of every channel of every image of `src`, on the device (crg_resample_u8), equal
+    to PIL's bytes.  src: [N, C, h, w], uint8, or fp32 in [0, 1] that is quantised as (255.0 * clamp(s, 0, 1)) -> uint8 (truncation);
+    any strides (contiguous, channels-last, a view), never written.  size = (H, W) of the result; window = (x0, y0, w, h) in src,
+    default the whole image - taps stay inside the window.  The result goes to the H x W rectangle at out_offset = (x, y) of `out`
+    ([N, C, rows, columns], uint8 or fp32, any strides, no overlap with src; by default a new contiguous [N, C, H, W] tensor of
+    `out_dtype`): bytes for uint8, out_affine[0] * (v / 255.0) + out_affine[1] for fp32.  `fill`: the value every pixel of `out`
+    outside the rectangle gets (a byte value for uint8); None leaves them as they are.  Returns `out`."""
+    _need_cuda(src, out)
+    if src.dim() != 4 or src.dtype not in (torch.uint8, torch.float32):
+        raise L.CrgError(f"resample_u8: [N, C, h, w] uint8 or float32 source expected, got {tuple(src.shape)} {src.dtype}")
+    n, ch, sh, sw = src.shape
+    H, W = int(size[0]), int(size[1])
+    x0, y0, w, h = (0, 0, sw, sh) if window is None else (int(v) for v in window)
+    ox, oy = int(out_offset[0]), int(out_offset[1])
+    if out is None:
+        if out_dtype not in (torch.uint8, torch.float32):
+            raise L.CrgError(f"resample_u8: out_dtype must be uint8 or float32, got {out_dtype}")
+        if H < 1 or W < 1 or n * ch < 1:
+            raise L.CrgError(f"resample_u8: empty result ({n}x{ch} planes of {H}x{W})")
+        if (ox, oy) != (0, 0):
+            raise L.CrgError("resample_u8: out_offset needs an `out` tensor")
+        out = torch.empty((n, ch, H, W), dtype=out_dtype, device=src.device)
+    elif out.dim() != 4 or out.dtype not in (torch.uint8, torch.float32) or tuple(out.shape[:2]) != (n, ch) or out.device != src.device:
+        raise L.CrgError(f"resample_u8: uint8 or float32 out of shape ({n}, {ch}, rows, columns) on {src.device} expected, got "
+                         f"{tuple(out.shape)} {out.dtype} on {out.device}")
+    if w < 1 or h < 1:
+        raise L.CrgError(f"resample_u8: empty window {(x0, y0, w, h)}")
+    a = L.ResampleArgs()
+    a.src, a.src_u8 = src.data_ptr(), 1 if src.dtype == torch.uint8 else 0
+    a.src_sn, a.src_sc, a.src_sy, a.src_sx = src.stride()
+    a.src_h, a.src_w = sh, sw
+    a.x0, a.y0, a.w, a.h = x0, y0, w, h
+    a.N, a.C, a.W, a.H = n, ch, W, H
+    a.ksize_x, kx, xb = _lanczos_device_tables(w, W, src.device)
+    a.ksize_y, ky, yb = _lanczos_device_tables(h, H, src.device)
+    a.kx, a.x_bounds, a.ky, a.y_bounds = kx.data_ptr(), xb.data_ptr(), ky.data_ptr(), yb.data_ptr()
+    a.dst, a.dst_u8 = out.data_ptr(), 1 if out.dtype == torch.uint8 else 0
+    a.dst_sn, a.dst_sc, a.dst_sy, a.dst_sx = out.stride()
+    a.dst_h, a.dst_w = out.shape[2], out.shape[3]
+    a.ox, a.oy = ox, oy
+    a.out_a, a.out_b = float(out_affine[0]), float(out_affine[1])
+    a.fill, a.fill_value = (0, 0.0) if fill is None else (1, float(fill))
+    hd = _h(src)
+    L.check(L.load().crg_resample_u8(hd, _st(), C.byref(a)), hd, "crg_resample_u8")
+    return _written(out)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

@@ -184,6 +184,23 @@ def _upscaler(name: str) -> str:
     return key
 
 
+RESAMPLERS = ("host", "device")  # where the pixel-space Lanczos glue runs: PIL on the host, or ops.resample_u8
+
+
+def _resampler(name: str) -> str:
+    if name not in RESAMPLERS:
+        raise ValueError(f"unknown resample {name!r} (one of {list(RESAMPLERS)})")
+    return name
+
+
+def _lanczos_scaled(PP, images: torch.Tensor, width: int, height: int, resample: str, signed: bool) -> torch.Tensor:
+    """postprocess.upscale_uint8 on the host or on the device; `signed`: * 2 - 1 behind it (folded into the device store)."""
+    if resample == "device":
+        return PP.upscale_uint8_device(images, width, height, (2.0, -1.0) if signed else (1.0, 0.0))
+    up = PP.upscale_uint8(images, width, height).contiguous()
+    return up * 2.0 - 1.0 if signed else up
+
+
 def _control_cond(c, uc, hint):
     """The two dict conditionings of a ControlNet run, holding the SAME hint object (image_generator.py:839-846, guess_mode False), so
     that the doubled c_concat gets the CFG mark (samplers.cat_cond_dict)."""
@@ -215,7 +232,7 @@ def txt2img_hires(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tens
                   cfg_scale: float = 7.5, height: int = 512, width: int = 512, factor: float = 2.0, strength: float = 0.5,
                   x0: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, noise_sampler: Optional[Callable] = None,
                   decode: bool = True, upscaler: str = "latent", hint: Optional[torch.Tensor] = None,
-                  hint_hires: Optional[torch.Tensor] = None, enc_noise: Optional[torch.Tensor] = None):
+                  hint_hires: Optional[torch.Tensor] = None, enc_noise: Optional[torch.Tensor] = None, resample: str = "host"):
     """Hires-fix (image_generator.py:889-932, :958-999, :1020-1098): txt2img at (height, width), an upscale by `factor`, forward
     diffusion to t_enc = int(strength * steps) (k_diffusion_samplers.py:255-296) and a denoise of the last t_enc + 1 sigmas at the
     larger size (img2img_sampling :192-211, :227-246).  `sampler`: a SAMPLERS key or Cremage's menu name, used by both passes.
@@ -229,9 +246,13 @@ def txt2img_hires(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tens
     `hint` ([b,3,height,width] in [0,1], ControlLDM only): both passes run dict conditioning; the second pass uses `hint_hires`
     ([b,3,height*factor,width*factor]), by default postprocess.upscale_uint8(hint) - the same approximation, of scale_control_image
     (:552-562).  The ControlNet's one-entry hint cache then holds the second pass' guided hint.  Returns (images, latents, base
-    latents)."""
+    latents).
+    `resample` ("host", the default, or "device"): where upscale_uint8 runs with upscaler "lanczos" - the upscaler's own and the default
+    hint_hires'; the "latent" route is not changed by it.  "device" is postprocess.upscale_uint8_device: one launch, no transfer and no synchronisation between the passes, the
+    same tensors to the bit."""
     from . import postprocess as PP
     upscaler = _upscaler(upscaler)
+    resample = _resampler(resample)
     b = c.shape[0]
     smp = _sampler(sampler)[1](ldm)
     smp.noise_sampler = noise_sampler
@@ -243,13 +264,13 @@ def txt2img_hires(ldm: LatentDiffusion, c: torch.Tensor, uc: Optional[torch.Tens
     if upscaler == "latent":
         z_enc = upscale_encode_latents(smp, base, factor, t_enc, steps, fwd_noise, fused=None if hint is not None else False)
     else:
-        scaled = PP.upscale_uint8(decode_images(ldm, base), big_w, big_h).contiguous() * 2.0 - 1.0
+        scaled = _lanczos_scaled(PP, decode_images(ldm, base), big_w, big_h, resample, True)
         init_latent = ldm.get_first_stage_encoding(ldm.encode_first_stage(scaled), enc_noise)
         z_enc = smp.stochastic_encode(init_latent, torch.tensor([t_enc] * b, device=init_latent.device), sampling_steps=steps,
                                       noise=fwd_noise)
     if hint is not None:
         if hint_hires is None:
-            hint_hires = PP.upscale_uint8(hint, big_w, big_h).contiguous()
+            hint_hires = _lanczos_scaled(PP, hint, big_w, big_h, resample if upscaler == "lanczos" else "host", False)
         cond, ucond = _control_cond(c, uc, hint_hires)
     samples, _ = smp.sample(S=steps, conditioning=cond, batch_size=b, shape=list(z_enc.shape[1:]), verbose=False,
                             unconditional_guidance_scale=cfg_scale, unconditional_conditioning=ucond, x0=z_enc, denoising_steps=t_enc)
@@ -398,7 +419,7 @@ def txt2img_sdxl_hires(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: fl
                        factor: float = 2.0, strength: float = 0.3, upscaler: str = "latent", c_hires: Optional[dict] = None,
                        uc_hires: Optional[dict] = None, x0: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None,
                        enc_noise: Optional[torch.Tensor] = None, sampler: str = "euler_edm", discretization: str = "legacy_ddpm",
-                       sampler_options: Optional[dict] = None, decode: bool = True):
+                       sampler_options: Optional[dict] = None, decode: bool = True, resample: str = "host"):
     """SDXL hires-fix (sdxl_image_generator.py:166-230): txt2img at (height, width), then an img2img pass at `strength` on the result
     upscaled by `factor` (run_img2img -> do_img2img, sdxl_image_generator_utils.py:986-1017, which adds noise).  `upscaler`:
       "latent"  - bilinear F.interpolate of the base latents, no VAE in between (skip_encode): DiffusionEngine.img2img_latent, on
@@ -410,9 +431,11 @@ def txt2img_sdxl_hires(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: fl
     hands in what it gives.  None reuses c / uc - which DIFFERS from Cremage: the size embedding then still says (height, width).
     The reference runs the second pass one image at a time with a fresh randn each; here the batch runs at once - the same arithmetic
     per image - and `fwd_noise` ([b,4,H*factor/8,W*factor/8]) is the noise of the whole batch.  Both passes use `sampler`,
-    `discretization` and `sampler_options` (as in txt2img_sdxl).  Returns (images or None, latents, base latents)."""
+    `discretization` and `sampler_options` (as in txt2img_sdxl).  `resample`: where the "lanczos" upscaler runs, as in txt2img_hires.
+    Returns (images or None, latents, base latents)."""
     from . import postprocess as PP
     upscaler = _upscaler(upscaler)
+    resample = _resampler(resample)
     c2, uc2 = (c if c_hires is None else c_hires), (uc if uc_hires is None else uc_hires)
     smp = dict(sampler=sampler, discretization=discretization, options=sampler_options)
     first, base = txt2img_sdxl(eng, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0,
@@ -421,7 +444,7 @@ def txt2img_sdxl_hires(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: fl
     if upscaler == "latent":
         samples = eng.img2img_latent(base, c2, uc2, steps, strength, cfg_scale, fwd_noise=fwd_noise, factor=factor, **smp)
     else:
-        scaled = PP.upscale_uint8(first, int(width * factor), int(height * factor)).contiguous() * 2.0 - 1.0
+        scaled = _lanczos_scaled(PP, first, int(width * factor), int(height * factor), resample, True)
         samples = eng.img2img(scaled, c2, uc2, steps, strength, cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise, **smp)
     if not decode:
         return None, samples, base
@@ -499,14 +522,18 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
 @torch.no_grad()
 def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps: int = 30, strength: float = 0.3, cfg_scale: float = 5.0,
                   target_edge_len: int = 1024, enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None,
-                  sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
+                  sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None,
+                  resample: str = "host"):
     """The auto-face-fix second pass with the REFERENCE's host-side glue (cremage_amd.postprocess: buffer / clamp / aspect-preserving
     Lanczos resize / white padding / un-pad / resize back / paste, face_detector_engine.py:152-288) around the UNet re-entry
     (`img2img_sdxl`, strength 0.3).  images [b,3,H,W] in [0,1]; faces[i] = list of (x, y, w, h) boxes of image i (the detector is out
     of scope).  Differences from the reference that remain: plain paste instead of cv.seamlessClone (no OpenCV here), and one
     conditioning row per image instead of a gender-prefixed prompt.  `sampler` / `discretization` / `sampler_options` as in
-    txt2img_sdxl.  Returns [b,3,H,W] in [0,1] on the images' device."""
+    txt2img_sdxl.  `resample` ("host", the default, or "device"): "device" keeps the image on the GPU (postprocess.face_fix_device: two
+    launches of ops.resample_u8 per face instead of two transfers, two synchronisations and the PIL calls) and returns the same
+    tensor to the bit.  Returns [b,3,H,W] in [0,1] on the images' device."""
     from . import postprocess as PP
+    resample = _resampler(resample)
     out = []
     for i in range(images.shape[0]):
         ci = {k: v[i:i + 1] for k, v in c.items()}
@@ -518,6 +545,35 @@ def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps:
                                 fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None, sampler=sampler,
                                 discretization=discretization, sampler_options=sampler_options)
             return y
-        pil = PP.face_fix(PP.unit_tensor_to_pil(images[i]), faces[i], i2i, target_edge_len)
-        out.append((PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5)
+        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample))
+    return torch.stack(out).to(images.device)
+
+
+def _face_fix_one(PP, image: torch.Tensor, faces, i2i: Callable, target_edge_len: int, resample: str) -> torch.Tensor:
+    """One image through postprocess.face_fix (PIL, host) or face_fix_device -> [3,H,W] fp32, ((u / 255 * 2 - 1) + 1) * 0.5 either way."""
+    if resample == "device":
+        u8 = PP.face_fix_device(image, faces, i2i, target_edge_len)
+        return (PP.u8_to_unit_device(u8[None], (2.0, -1.0))[0] + 1.0) * 0.5
+    pil = PP.face_fix(PP.unit_tensor_to_pil(image), faces, i2i, target_edge_len)
+    return (PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5
+
+
+@torch.no_grad()
+def face_fix_sd15(ldm: LatentDiffusion, images: torch.Tensor, faces, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 20,
+                  strength: float = 0.3, cfg_scale: float = 7.5, target_edge_len: int = 512, enc_noise: Optional[torch.Tensor] = None,
+                  fwd_noise: Optional[torch.Tensor] = None, resample: str = "host"):
+    """The SD1.5 auto-face-fix second pass (face_detector_engine.py `face_fix_generator_model_type` SD 1.5: the same crop / pad / paste
+    glue as face_fix_sdxl around `img2img`, whose sampler the reference forces to DDIM).  images [b,3,H,W] in [0,1]; faces[i] = list of
+    (x, y, w, h) boxes of image i; c / uc: [b, 77*n, 768], one conditioning row per image; enc_noise [b,4,edge/8,edge/8] / fwd_noise: row i
+    is the noise of every face of image i.  `resample` as in face_fix_sdxl.  Returns [b,3,H,W] in [0,1] on the images' device."""
+    from . import postprocess as PP
+    resample = _resampler(resample)
+    out = []
+    for i in range(images.shape[0]):
+        def i2i(x, i=i):
+            y, _ = img2img(ldm, x.to(images.device), c[i:i + 1], uc[i:i + 1] if uc is not None else None, steps=steps, strength=strength,
+                           cfg_scale=cfg_scale, enc_noise=enc_noise[i:i + 1] if enc_noise is not None else None,
+                           fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None)
+            return y
+        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample))
     return torch.stack(out).to(images.device)

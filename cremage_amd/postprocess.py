@@ -20,7 +20,12 @@ that a Cremage user finds the whole second-pass chain:
                                    (:357-398, use_seamless_clone = False): 11x11 Gaussian blur of the mask, alpha blend over the
                                    original, crop of the padding.  The blur is restated in numpy (see `gaussian_blur_11`).
 
-Pure Python + PIL + numpy; nothing here touches the HIP library.
+Pure Python + PIL + numpy; nothing above the "device twins" section touches the HIP library.
+
+Device twins (`resample_u8_host` and the `*_device` functions): the same arithmetic with the image staying on the GPU.  PIL resizes
+8-bit images in fixed point (Resample.c: 22-bit integer coefficients, a horizontal pass clipped to uint8, then a vertical one), so the
+Lanczos resize is restated exactly - `resample_u8_host` in numpy as the CPU proof of the tables, cremage_amd.ops.resample_u8 as one
+launch - and the twins return what the host functions return, to the bit.  The host functions stay the default.
 """
 from __future__ import annotations
 
@@ -148,6 +153,96 @@ def upscale_uint8(samples: torch.Tensor, width: int, height: int) -> torch.Tenso
     for i in range(u8.shape[0]):
         out[i] = np.asarray(Image.fromarray(u8[i]).resize((width, height), resample=Image.LANCZOS), dtype=np.float32)
     return (torch.from_numpy(out).permute(0, 3, 1, 2) / 255.0).float().to(samples.device)
+
+
+# ---------------------------------------------------------------------------------------------- device twins
+def resample_u8_host(u8_hwc: np.ndarray, width: int, height: int) -> np.ndarray:
+    """`np.asarray(Image.fromarray(a).resize((width, height), Image.LANCZOS))` of an uint8 [h, w] or [h, w, c] array, restated in numpy on
+    cremage_amd.ops.lanczos_tables: PIL's two passes (Resample.c ImagingResampleHorizontal_8bpc, then Vertical_8bpc), each
+    clip8((2^21 + sum_j in[min + j] * k[j]) >> 22) in 32-bit integers, with an uint8 image between them; a pass whose length does not
+    change is skipped.  The horizontal pass runs only over the source rows the vertical one reads, as in PIL.  This is the arithmetic
+    of crg_resample_u8 and the CPU proof of its tables."""
+    from .ops import RESAMPLE_BITS, lanczos_tables
+    a = np.asarray(u8_hwc)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError(f"resample_u8_host: uint8 [h, w] or [h, w, c] array expected, got {a.dtype} {a.shape}")
+
+    def one_pass(img, axis, out_size):
+        in_size = img.shape[axis]
+        if in_size == out_size:
+            return img
+        _, bounds, coeffs = lanczos_tables(in_size, out_size)
+        src = np.moveaxis(img, axis, 0).astype(np.int32)
+        out = np.empty((out_size,) + src.shape[1:], dtype=np.uint8)
+        for i, (lo, cnt) in enumerate(bounds):
+            k = np.asarray(coeffs[i][:cnt], dtype=np.int32).reshape((cnt,) + (1,) * (src.ndim - 1))
+            acc = (src[lo:lo + cnt] * k).sum(axis=0, dtype=np.int32) + np.int32(1 << (RESAMPLE_BITS - 1))
+            out[i] = np.clip(acc >> RESAMPLE_BITS, 0, 255).astype(np.uint8)
+        return np.moveaxis(out, 0, axis)
+
+    if a.shape[0] != height and a.shape[1] != width:  # both passes: only the rows the vertical pass reads
+        _, yb, _ = lanczos_tables(a.shape[0], height)
+        first, last = yb[0][0], yb[-1][0] + yb[-1][1]
+        t = np.zeros((a.shape[0], width) + a.shape[2:], dtype=np.uint8)
+        t[first:last] = one_pass(a[first:last], 1, width)
+        return one_pass(t, 0, height)
+    return one_pass(one_pass(a, 1, width), 0, height)
+
+
+def upscale_uint8_device(samples: torch.Tensor, width: int, height: int, affine: Tuple[float, float] = (1.0, 0.0)) -> torch.Tensor:
+    """`upscale_uint8` without leaving the device: one launch (cremage_amd.ops.resample_u8) quantises, resizes and stores
+    affine[0] * (v / 255.0) + affine[1] - (1, 0) is upscale_uint8's result to the bit, (2, -1) folds in the `* 2 - 1` that precedes the
+    VAE encode.  samples: [b, c, h, w] fp32 in [0, 1] on the device, any strides.  The same APPROXIMATION of cv2.INTER_LANCZOS4."""
+    from . import ops
+    return ops.resample_u8(samples, (height, width), out_affine=affine, out_dtype=torch.float32)
+
+
+def crop_and_pad_device(image: torch.Tensor, plan: FaceCropPlan) -> torch.Tensor:
+    """`pil_to_unit_tensor(crop_and_pad(image, plan))` on the device: image [1, 3, H, W] (uint8, or fp32 in [0, 1]) -> [1, 3, edge, edge] fp32
+    in [-1, 1], the crop rectangle resized to (new_w, new_h) at (pad_x, pad_y) of a white square."""
+    from . import ops
+    out = torch.empty((image.shape[0], image.shape[1], plan.edge, plan.edge), dtype=torch.float32, device=image.device)
+    return ops.resample_u8(image, (plan.new_h, plan.new_w), window=(plan.x, plan.y, plan.w, plan.h), out=out,
+                           out_offset=(plan.pad_x, plan.pad_y), out_affine=(2.0, -1.0), fill=1.0)
+
+
+def unpad_resize_paste_device(working_u8: torch.Tensor, updated: torch.Tensor, plan: FaceCropPlan) -> torch.Tensor:
+    """`paste_face(image, unpad_and_resize(unit_tensor_to_pil(updated[0]), plan), plan)` on the device, IN PLACE: the inner box of
+    `updated` ([1, 3, edge, edge] fp32 in [0, 1]) is quantised, resized to the crop rectangle's size and written over that rectangle
+    of `working_u8` ([1, 3, H, W] uint8).  Nothing outside the rectangle is touched.  Returns working_u8."""
+    from . import ops
+    return ops.resample_u8(updated, (plan.h, plan.w), window=(plan.pad_x, plan.pad_y, plan.new_w, plan.new_h), out=working_u8,
+                           out_offset=(plan.x, plan.y))
+
+
+def face_fix_device(image: torch.Tensor, faces: Iterable[Sequence[float]], img2img_fn: Callable[[torch.Tensor], torch.Tensor],
+                    target_edge_len: int = 512) -> torch.Tensor:
+    """`face_fix` with the image staying on the device.  image: [3, H, W] fp32 in [0, 1] (quantised ONCE, as unit_tensor_to_pil does) or
+    uint8; the working image is a device uint8 tensor, every face works on what the previous one left, and `img2img_fn` gets and
+    returns device tensors ([1, 3, edge, edge] in [-1, 1] -> in [0, 1]).  Plain paste only (see paste_face).  Returns the working image,
+    uint8 [3, H, W] on the device - the bytes of the PIL image face_fix returns."""
+    if image.dim() != 3:
+        raise ValueError(f"face_fix_device: [3, H, W] image expected, got {tuple(image.shape)}")
+    if image.dtype == torch.uint8:
+        work = image.detach().clone()[None]
+    else:
+        work = (255.0 * image.detach().float().clamp(0, 1)).to(torch.uint8)[None].contiguous()
+    size = (work.shape[3], work.shape[2])
+    for face in faces:
+        plan = face_crop_plan(face, size, target_edge_len)
+        out = img2img_fn(crop_and_pad_device(work, plan))
+        if out.shape[-2:] != (plan.edge, plan.edge):
+            raise ValueError(f"img2img returned {tuple(out.shape)} for a {plan.edge}x{plan.edge} input")
+        unpad_resize_paste_device(work, out[:1].float(), plan)
+    return work[0]
+
+
+def u8_to_unit_device(u8: torch.Tensor, affine: Tuple[float, float] = (1.0, 0.0)) -> torch.Tensor:
+    """[N, C, H, W] device uint8 -> fp32 affine[0] * (v / 255.0) + affine[1], the division correctly rounded as numpy's and ATen's CPU
+    division are (ATen's DEVICE division by a scalar multiplies by the reciprocal, which differs in the last bit for some bytes):
+    pil_to_unit_tensor's arithmetic with affine (2, -1).  The same launch as the resizes, with the pass-skipping one-tap tables."""
+    from . import ops
+    return ops.resample_u8(u8, tuple(u8.shape[2:]), out_affine=affine, out_dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------- inpainting

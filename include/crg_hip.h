@@ -476,6 +476,48 @@ int crg_cfg_kstep(crg_ctx* ctx, void* stream, const crg_kstep_args* args);
 int crg_resize_noise(crg_ctx* ctx, void* stream, const void* x, const void* noise, void* out, int64_t planes, int h, int w, int H, int W,
                      const int* y_idx, const float* y_wt, const int* x_idx, const float* x_wt, float a, float s, float d);
 
+/* PIL's 8-bit two-pass resize (Resample.c, ImagingResampleHorizontal_8bpc / Vertical_8bpc) of a window of an image, on the device:
+ * the pixel-space Lanczos glue of hires fix (ml_utils.py:28-71) and of the auto face fix (face_detector_engine.py:152-288: crop ->
+ * resize -> white padding, and un-pad -> resize -> paste).  Per image n and channel c, with 32-bit integer accumulation:
+ *   q      = the source, uint8, or fp32 as (uint8)(255.0f * min(max(s, 0), 1)) (truncation); rows / columns are those of the WINDOW
+ *            (x0, y0, w, h): a crop, then a resize - taps never reach outside the window
+ *   t[y][X] = clip8((2^21 + sum_j q[y][xmin + j] * kx[X][j]) >> 22),   (xmin, count) = x_bounds[X]     uint8 between the passes, as PIL
+ *   v[Y][X] = clip8((2^21 + sum_j t[ymin + j][X] * ky[Y][j]) >> 22),   (ymin, count) = y_bounds[Y]
+ *   dst[n][c][oy + Y][ox + X] = v (uint8), or out_a * ((float)v / 255.0f) + out_b (fp32: correctly rounded division, one rounding per
+ *            operation, no contraction)
+ * kx int32 [W][ksize_x] and x_bounds int32 [W][2], ky [H][ksize_y] and y_bounds [H][2] are host-built DEVICE tables (PIL's
+ * precompute_coeffs + normalize_coeffs_8bpc).  PIL skips a pass whose input and output lengths are equal; the one-tap table
+ * {2^22}, bounds (i, 1), is that skip to the bit.  Bounds are clamped to the window and to ksize, so a wrong table gives wrong
+ * values, never an out-of-bounds access; they must not decrease along the axis (PIL's do not).
+ * Source and destination are strided [N][C][rows][columns] tensors (strides in ELEMENTS: contiguous NCHW and channels-last alike) that
+ * must not overlap.  fill != 0: every destination pixel outside the W x H rectangle at (ox, oy) is set to fill_value (a byte value
+ * for an uint8 destination) by a second launch - the white square of crop_and_pad; fill == 0: nothing outside the rectangle is
+ * written - the paste.  No host synchronisation, no atomics, no allocation; the intermediate t lives in LDS. */
+typedef struct {
+  const void* src;         /* [N][C][src_h][src_w], strided */
+  int src_u8;              /* 1: uint8, 0: fp32 in [0, 1] */
+  int64_t src_sn, src_sc, src_sy, src_sx; /* element strides */
+  int src_h, src_w;        /* the whole source image: the window must lie inside */
+  int x0, y0, w, h;        /* the window */
+  int N, C;
+  int W, H;                /* the result */
+  const int* kx;           /* [W][ksize_x] */
+  const int* x_bounds;     /* [W][2]: xmin, count */
+  int ksize_x;
+  const int* ky;           /* [H][ksize_y] */
+  const int* y_bounds;     /* [H][2]: ymin, count */
+  int ksize_y;
+  void* dst;               /* [N][C][dst_h][dst_w], strided */
+  int dst_u8;              /* 1: uint8, 0: fp32 */
+  int64_t dst_sn, dst_sc, dst_sy, dst_sx; /* element strides */
+  int dst_h, dst_w;        /* the whole destination image: the rectangle must lie inside */
+  int ox, oy;              /* where the result goes */
+  float out_a, out_b;      /* fp32 destination only */
+  int fill;                /* != 0: write fill_value outside the rectangle */
+  float fill_value;
+} crg_resample_args;
+int crg_resample_u8(crg_ctx* ctx, void* stream, const crg_resample_args* args);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
