@@ -128,6 +128,22 @@ class ResampleArgs(C.Structure):
     ]
 
 
+class PoissonArgs(C.Structure):
+    _fields_ = [
+        ("image", c_void_p),
+        ("img_sn", c_int64), ("img_sc", c_int64), ("img_sy", c_int64), ("img_sx", c_int64),
+        ("img_h", c_int), ("img_w", c_int),
+        ("patch", c_void_p),
+        ("pat_sn", c_int64), ("pat_sc", c_int64), ("pat_sy", c_int64), ("pat_sx", c_int64),
+        ("N", c_int),
+        ("h", c_int), ("w", c_int),
+        ("x", c_int), ("y", c_int),
+        ("margin", c_int),
+        ("s_rows", c_void_p), ("s_cols", c_void_p), ("rden", c_void_p),
+        ("work", c_void_p), ("field", c_void_p),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -186,6 +202,7 @@ SIGNATURES = {
     "crg_resize_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_float, c_float, c_float]),
     "crg_resample_u8": (c_int, [c_void_p, c_void_p, C.POINTER(ResampleArgs)]),
+    "crg_poisson_clone": (c_int, [c_void_p, c_void_p, C.POINTER(PoissonArgs)]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

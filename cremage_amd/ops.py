@@ -1392,6 +1392,85 @@ def resample_u8(src: torch.Tensor, size: Tuple[int, int], window: Optional[Tuple
     return _written(out)
 
 
+# ---------------------------------------------------------------------------------- gradient-domain (Poisson) paste
+@functools.lru_cache(maxsize=64)
+def poisson_tables(k: int):
+    """(S_k, lam_k) of the type-I sine transform of length k, float64 numpy arrays built on the host: S_k[a, b] = sin(pi (a+1)(b+1) / (k+1))
+    (symmetric, S_k S_k = (k+1)/2 I) and lam_k[a] = 2 cos(pi (a+1) / (k+1)) - 2, the eigenvalues of the 1-D second difference with zero
+    boundaries.  The tables of postprocess.poisson_clone_host and, rounded once to fp32, of crg_poisson_clone.  Cached per k; read-only
+    arrays, so the cached value cannot be written."""
+    import numpy as np
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"poisson_tables: the size must be positive (got {k})")
+    i = np.arange(1, k + 1, dtype=np.float64)
+    s = np.sin(np.pi * np.outer(i, i) / (k + 1))
+    lam = 2.0 * np.cos(np.pi * i / (k + 1)) - 2.0
+    s.setflags(write=False)
+    lam.setflags(write=False)
+    return s, lam
+
+
+_POISSON_TABLES = {}  # ("s", k, device) -> fp32 S_k, ("r", n, m, device) -> fp32 reciprocal denominators, on the device: uploaded once
+
+
+def _poisson_device_tables(n: int, m: int, device):
+    out = []
+    for k in (n, m):
+        t = _POISSON_TABLES.get(("s", k, device))
+        if t is None:
+            t = _POISSON_TABLES[("s", k, device)] = torch.tensor(poisson_tables(k)[0], dtype=torch.float32).to(device)
+        out.append(t)
+    r = _POISSON_TABLES.get(("r", n, m, device))
+    if r is None:
+        den = (poisson_tables(n)[1][:, None] + poisson_tables(m)[1][None, :]) * ((n + 1) * (m + 1) / 4.0)
+        r = _POISSON_TABLES[("r", n, m, device)] = torch.tensor(1.0 / den, dtype=torch.float32).to(device)
+    return out[0], out[1], r
+
+
+def poisson_clone(image_u8: torch.Tensor, patch_u8: torch.Tensor, offset: Tuple[int, int], margin: int = 3,
+                  field_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """postprocess.poisson_clone_host on the device, IN PLACE (crg_poisson_clone): the gradient-domain paste of patch_u8 [N, 3, h, w] into
+    image_u8 [N, 3, H, W] with its top-left corner at offset = (x, y), every image and channel on its own.  Both uint8, any strides
+    (contiguous, channels-last, a view), no overlap.  Only the rectangle inset by 2 is written; a patch with h < 5 or w < 5 has no
+    interior and nothing is launched.  field_out: contiguous fp32 [N, 3, h-4, w-4] that receives the solution before rounding.  The
+    solve is fp32 (see DESIGN f11 for its error against the host's float64).  Returns image_u8."""
+    _need_cuda(image_u8, patch_u8, field_out)
+    if image_u8.dtype != torch.uint8 or patch_u8.dtype != torch.uint8:
+        raise ValueError(f"poisson_clone: uint8 image and patch expected, got {image_u8.dtype} and {patch_u8.dtype}")
+    if image_u8.dim() != 4 or patch_u8.dim() != 4 or image_u8.shape[1] != 3 or tuple(patch_u8.shape[:2]) != tuple(image_u8.shape[:2]):
+        raise ValueError(f"poisson_clone: image [N, 3, H, W] and patch [N, 3, h, w] expected, got {tuple(image_u8.shape)} and {tuple(patch_u8.shape)}")
+    n_img, _, H, W = image_u8.shape
+    h, w = int(patch_u8.shape[2]), int(patch_u8.shape[3])
+    x, y, margin = int(offset[0]), int(offset[1]), int(margin)
+    if n_img < 1 or h < 1 or w < 1 or x < 0 or y < 0 or x + w > W or y + h > H:
+        raise ValueError(f"poisson_clone: patch {h}x{w} at (x {x}, y {y}) is empty or lies outside the {H}x{W} image")
+    if margin < 0:
+        raise ValueError(f"poisson_clone: margin must not be negative (got {margin})")
+    n, m = h - 4, w - 4
+    if field_out is not None and (field_out.dtype != torch.float32 or not field_out.is_contiguous() or field_out.device != image_u8.device or
+                                  tuple(field_out.shape) != (n_img, 3, max(n, 0), max(m, 0))):
+        raise ValueError(f"poisson_clone: contiguous fp32 field_out of shape {(n_img, 3, max(n, 0), max(m, 0))} on {image_u8.device} expected")
+    if patch_u8.device != image_u8.device:
+        raise L.CrgError(f"poisson_clone: image on {image_u8.device}, patch on {patch_u8.device}")
+    if n < 1 or m < 1:
+        return image_u8
+    a = L.PoissonArgs()
+    a.image, a.patch = image_u8.data_ptr(), patch_u8.data_ptr()
+    a.img_sn, a.img_sc, a.img_sy, a.img_sx = image_u8.stride()
+    a.pat_sn, a.pat_sc, a.pat_sy, a.pat_sx = patch_u8.stride()
+    a.img_h, a.img_w, a.N, a.h, a.w, a.x, a.y, a.margin = H, W, n_img, h, w, x, y, margin
+    s_rows, s_cols, rden = _poisson_device_tables(n, m, image_u8.device)
+    work = torch.empty((2, n_img, 3, n, m), dtype=torch.float32, device=image_u8.device)
+    a.s_rows, a.s_cols, a.rden, a.work = s_rows.data_ptr(), s_cols.data_ptr(), rden.data_ptr(), work.data_ptr()
+    a.field = field_out.data_ptr() if field_out is not None else None
+    hd = _h(image_u8)
+    L.check(L.load().crg_poisson_clone(hd, _st(), C.byref(a)), hd, "crg_poisson_clone")
+    if field_out is not None:
+        _written(field_out)
+    return _written(image_u8)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

@@ -492,7 +492,8 @@ def txt2img_sdxl_refined(base, refiner, c: dict, uc: dict, c2: dict, uc2: dict, 
 def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
                          fix_size: Optional[int] = None, strength: float = 0.3, x0: Optional[torch.Tensor] = None,
                          enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None, paste: bool = True,
-                         sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None):
+                         sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None,
+                         paste_mode: str = "paste"):
     """BASELINE config 5: SDXL txt2img, then the auto-face-fix second pass on one region per image - the UNet RE-ENTRY on a crop.
 
     Reference flow (modules/sdxl/sdxl_pipeline/sdxl_image_generator_utils.py:559-772 txt2img, then per detected face
@@ -502,9 +503,15 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
     In scope here is the numeric path (both UNet passes, VAE encode / decode); the glue around it is deliberately plain PyTorch:
     `boxes` = one (top, left, size) per image instead of the face detector (out of scope), the two resizes are
     F.interpolate(bilinear, antialias off) instead of cv2 Lanczos (not built), the paste is a hard-edged copy.
-    Both passes use `sampler`, `discretization` and `sampler_options` (as in txt2img_sdxl).
+    Both passes use `sampler`, `discretization` and `sampler_options` (as in txt2img_sdxl).  `paste_mode` "poisson": the paste is
+    postprocess's gradient-domain one on the device (ops.poisson_clone on the images quantised to uint8 as unit_tensor_to_pil does, so
+    the whole result is then a multiple of 1/255), the stated approximation of the reference's cv.seamlessClone; the default stays the copy.
     Returns (final images [b,3,H,W] in [0,1], first-pass images, second-pass crops at `fix_size`)."""
     import torch.nn.functional as F
+    from . import postprocess as PP
+    paste_mode = _paste_mode(PP, paste_mode)
+    if paste_mode == "seamless":
+        raise NotImplementedError("cv.seamlessClone (Poisson blending) needs OpenCV, which this build cannot import or pin against")
     smp = dict(sampler=sampler, discretization=discretization, sampler_options=sampler_options)
     first, _ = txt2img_sdxl(eng, c, uc, steps=steps, cfg_scale=cfg_scale, height=height, width=width, x0=x0, **smp)
     fix = fix_size or height
@@ -513,7 +520,14 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
     fixed, _ = img2img_sdxl(eng, crops * 2.0 - 1.0, c, uc, steps=steps, strength=strength, cfg_scale=cfg_scale, enc_noise=enc_noise,
                             fwd_noise=fwd_noise, **smp)
     out = first.clone()
-    if paste:
+    if paste and paste_mode == "poisson":
+        quantise = lambda v: (255.0 * v.float().clamp(0, 1)).to(torch.uint8)
+        u8 = quantise(first)
+        for i, (t, l, sz) in enumerate(boxes):
+            face = quantise(F.interpolate(fixed[i:i + 1], size=(sz, sz), mode="bilinear", align_corners=False))
+            ops.poisson_clone(u8[i:i + 1], face, (l, t), PP.POISSON_MARGIN)
+        out = PP.u8_to_unit_device(u8).to(first.dtype)
+    elif paste:
         for i, (t, l, sz) in enumerate(boxes):
             out[i, :, t:t + sz, l:l + sz] = F.interpolate(fixed[i:i + 1], size=(sz, sz), mode="bilinear", align_corners=False)[0]
     return out, first, fixed
@@ -523,17 +537,18 @@ def txt2img_sdxl_facefix(eng, c: dict, uc: dict, boxes, *, steps: int = 30, cfg_
 def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps: int = 30, strength: float = 0.3, cfg_scale: float = 5.0,
                   target_edge_len: int = 1024, enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None,
                   sampler: str = "euler_edm", discretization: str = "legacy_ddpm", sampler_options: Optional[dict] = None,
-                  resample: str = "host"):
+                  resample: str = "host", paste_mode: str = "paste"):
     """The auto-face-fix second pass with the REFERENCE's host-side glue (cremage_amd.postprocess: buffer / clamp / aspect-preserving
     Lanczos resize / white padding / un-pad / resize back / paste, face_detector_engine.py:152-288) around the UNet re-entry
     (`img2img_sdxl`, strength 0.3).  images [b,3,H,W] in [0,1]; faces[i] = list of (x, y, w, h) boxes of image i (the detector is out
-    of scope).  Differences from the reference that remain: plain paste instead of cv.seamlessClone (no OpenCV here), and one
+    of scope).  Differences from the reference that remain: plain paste instead of cv.seamlessClone (no OpenCV here; `paste_mode`
+    "poisson" is its stated approximation, postprocess.poisson_clone_host - on the device ops.poisson_clone, bytes within 1), and one
     conditioning row per image instead of a gender-prefixed prompt.  `sampler` / `discretization` / `sampler_options` as in
     txt2img_sdxl.  `resample` ("host", the default, or "device"): "device" keeps the image on the GPU (postprocess.face_fix_device: two
     launches of ops.resample_u8 per face instead of two transfers, two synchronisations and the PIL calls) and returns the same
     tensor to the bit.  Returns [b,3,H,W] in [0,1] on the images' device."""
     from . import postprocess as PP
-    resample = _resampler(resample)
+    resample, paste_mode = _resampler(resample), _paste_mode(PP, paste_mode)
     out = []
     for i in range(images.shape[0]):
         ci = {k: v[i:i + 1] for k, v in c.items()}
@@ -545,29 +560,35 @@ def face_fix_sdxl(eng, images: torch.Tensor, faces, c: dict, uc: dict, *, steps:
                                 fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None, sampler=sampler,
                                 discretization=discretization, sampler_options=sampler_options)
             return y
-        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample))
+        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample, paste_mode))
     return torch.stack(out).to(images.device)
 
 
-def _face_fix_one(PP, image: torch.Tensor, faces, i2i: Callable, target_edge_len: int, resample: str) -> torch.Tensor:
+def _paste_mode(PP, name: str) -> str:
+    if name != "seamless" and name not in PP.PASTE_MODES:  # "seamless" raises NotImplementedError where the paste happens
+        raise ValueError(f"unknown paste mode {name!r} (one of {list(PP.PASTE_MODES)})")
+    return name
+
+
+def _face_fix_one(PP, image: torch.Tensor, faces, i2i: Callable, target_edge_len: int, resample: str, paste_mode: str = "paste") -> torch.Tensor:
     """One image through postprocess.face_fix (PIL, host) or face_fix_device -> [3,H,W] fp32, ((u / 255 * 2 - 1) + 1) * 0.5 either way."""
     if resample == "device":
-        u8 = PP.face_fix_device(image, faces, i2i, target_edge_len)
+        u8 = PP.face_fix_device(image, faces, i2i, target_edge_len, paste_mode)
         return (PP.u8_to_unit_device(u8[None], (2.0, -1.0))[0] + 1.0) * 0.5
-    pil = PP.face_fix(PP.unit_tensor_to_pil(image), faces, i2i, target_edge_len)
+    pil = PP.face_fix(PP.unit_tensor_to_pil(image), faces, i2i, target_edge_len, paste_mode)
     return (PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5
 
 
 @torch.no_grad()
 def face_fix_sd15(ldm: LatentDiffusion, images: torch.Tensor, faces, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 20,
                   strength: float = 0.3, cfg_scale: float = 7.5, target_edge_len: int = 512, enc_noise: Optional[torch.Tensor] = None,
-                  fwd_noise: Optional[torch.Tensor] = None, resample: str = "host"):
+                  fwd_noise: Optional[torch.Tensor] = None, resample: str = "host", paste_mode: str = "paste"):
     """The SD1.5 auto-face-fix second pass (face_detector_engine.py `face_fix_generator_model_type` SD 1.5: the same crop / pad / paste
     glue as face_fix_sdxl around `img2img`, whose sampler the reference forces to DDIM).  images [b,3,H,W] in [0,1]; faces[i] = list of
     (x, y, w, h) boxes of image i; c / uc: [b, 77*n, 768], one conditioning row per image; enc_noise [b,4,edge/8,edge/8] / fwd_noise: row i
-    is the noise of every face of image i.  `resample` as in face_fix_sdxl.  Returns [b,3,H,W] in [0,1] on the images' device."""
+    is the noise of every face of image i.  `resample` and `paste_mode` as in face_fix_sdxl.  Returns [b,3,H,W] in [0,1] on the images' device."""
     from . import postprocess as PP
-    resample = _resampler(resample)
+    resample, paste_mode = _resampler(resample), _paste_mode(PP, paste_mode)
     out = []
     for i in range(images.shape[0]):
         def i2i(x, i=i):
@@ -575,5 +596,5 @@ def face_fix_sd15(ldm: LatentDiffusion, images: torch.Tensor, faces, c: torch.Te
                            cfg_scale=cfg_scale, enc_noise=enc_noise[i:i + 1] if enc_noise is not None else None,
                            fwd_noise=fwd_noise[i:i + 1] if fwd_noise is not None else None)
             return y
-        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample))
+        out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample, paste_mode))
     return torch.stack(out).to(images.device)

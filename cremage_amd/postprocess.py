@@ -9,8 +9,13 @@ that a Cremage user finds the whole second-pass chain:
   padded square -> img2img         (the UNet re-entry: cremage_amd.pipeline.img2img / img2img_sdxl)
   result -> un-pad, resize back    face_detector_engine.py:257-266
   paste                            face_detector_engine.py:268-288 uses cv.seamlessClone (NORMAL_CLONE); cv2 does not exist in this
-                                   image, so Poisson blending is NOT restated (it could not be pinned against the reference) - the
-                                   plain paste the reference keeps as a comment (:269) is what `paste_face` does, and says so
+                                   image, so it cannot be pinned against the reference: mode "seamless" stays reserved for a pinned
+                                   form and raises.  The default is the plain paste the reference keeps as a comment (:269).  Mode
+                                   "poisson" (`poisson_clone_host`) is NORMAL_CLONE with an all-white mask restated from the published
+                                   algorithm (Perez et al. 2003 as OpenCV implements it) - a stated APPROXIMATION, unpinned against
+                                   cv2, like `upscale_uint8`.  Its assumptions: the mask is eroded by a margin of 3, the region is
+                                   the rectangle inset by 1, bytes are rint (half to even) of the solution, and cv2's own fp32
+                                   arithmetic is not reproduced bit for bit (the system is solved in float64).
   PNG + generation_data            modules/sd/image_generator.py:1121-1212 (PngInfo.add_text("generation_data", json.dumps(...)))
   hires-fix pixel upscaler         image_generator.py:1020-1026 -> cremage/utils/ml_utils.py:28-71: cv2.resize(INTER_LANCZOS4) on uint8.
                                    cv2's 8x8 Lanczos-4 kernel is not PIL's Lanczos-3: `upscale_uint8` does the same uint8 round trip
@@ -25,7 +30,9 @@ Pure Python + PIL + numpy; nothing above the "device twins" section touches the 
 Device twins (`resample_u8_host` and the `*_device` functions): the same arithmetic with the image staying on the GPU.  PIL resizes
 8-bit images in fixed point (Resample.c: 22-bit integer coefficients, a horizontal pass clipped to uint8, then a vertical one), so the
 Lanczos resize is restated exactly - `resample_u8_host` in numpy as the CPU proof of the tables, cremage_amd.ops.resample_u8 as one
-launch - and the twins return what the host functions return, to the bit.  The host functions stay the default.
+launch - and the twins return what the host functions return, to the bit.  The host functions stay the default.  The "poisson" paste
+on the device (cremage_amd.ops.poisson_clone) solves in fp32: its bytes differ from the host's by at most 1, and only where the
+float64 solution lies next to a half-integer.
 """
 from __future__ import annotations
 
@@ -39,6 +46,8 @@ import numpy as np
 import torch
 
 FACE_BUFFER = 20  # face_detector_engine.py:158
+PASTE_MODES = ("paste", "poisson")  # "seamless" is reserved for a form pinned against cv2 and raises
+POISSON_MARGIN = 3  # ASSUMPTION: seamlessClone erodes the mask three times with a 3x3 kernel before it mixes the gradients
 
 
 @dataclass(frozen=True)
@@ -102,14 +111,100 @@ def unpad_and_resize(updated, plan: FaceCropPlan):
     return updated.crop(plan.inner_box).resize((plan.w, plan.h), resample=Image.LANCZOS)
 
 
+def _poisson_rhs(d: np.ndarray, s: np.ndarray, margin: int) -> np.ndarray:
+    """Steps 2-4 of poisson_clone_host for integer arrays d, s [hp, wp, c] -> F [hp - 2, wp - 2, c]: the divergence of the mixed forward
+    differences at the interior pixels, with the ring values of d moved to the right-hand side.  Integers, so exact."""
+    hp, wp = d.shape[:2]
+    k = np.zeros((hp, wp, 1), dtype=d.dtype)
+    k[margin:hp - margin, margin:wp - margin] = 1
+
+    def gx(f):
+        g = np.zeros_like(f)
+        g[:, :-1] = f[:, 1:] - f[:, :-1]
+        return g
+
+    def gy(f):
+        g = np.zeros_like(f)
+        g[:-1] = f[1:] - f[:-1]
+        return g
+    vx = k * gx(s) + (1 - k) * gx(d)
+    vy = k * gy(s) + (1 - k) * gy(d)
+    F = vx[1:-1, 1:-1] - vx[1:-1, :-2] + vy[1:-1, 1:-1] - vy[:-2, 1:-1]
+    F[0] -= d[0, 1:-1]
+    F[-1] -= d[-1, 1:-1]
+    F[:, 0] -= d[1:-1, 0]
+    F[:, -1] -= d[1:-1, -1]
+    return F
+
+
+def poisson_clone_host(image_u8_hwc: np.ndarray, patch_u8_hwc: np.ndarray, x: int, y: int, margin: int = POISSON_MARGIN, dtype=np.float64,
+                       return_field: bool = False):
+    """Gradient-domain paste of `patch_u8_hwc` [h, w, c] into `image_u8_hwc` [H, W, c] with its top-left corner at (x, y): OpenCV's
+    seamlessClone NORMAL_CLONE as the reference calls it (all-white mask, centre of the crop rectangle), restated from the published
+    algorithm and UNPINNED against cv2.  Every channel on its own, as real numbers:
+      1. region   d = image[y+1 : y+h-1, x+1 : x+w-1], s = patch[1 : h-1, 1 : w-1], both hp x wp = (h-2) x (w-2).  ASSUMPTION (inset of 1):
+                  cv2 zeroes the mask's one-pixel border, takes the bounding rectangle and centres it on (x + w//2, y + h//2), which
+                  gives this offset for both parities of w and h.
+      2. mask     k = 1 for margin <= i < hp - margin and margin <= j < wp - margin, else 0.  ASSUMPTION (margin 3): three erosions by a
+                  3x3 kernel.
+      3. field    vx = k (s[i, j+1] - s[i, j]) + (1 - k) (d[i, j+1] - d[i, j]); vy the same down the rows (forward differences)
+      4. rhs      L[i, j] = vx[i, j] - vx[i, j-1] + vy[i, j] - vy[i-1, j] at the interior pixels 1 <= i <= hp-2, 1 <= j <= wp-2
+      5. solve    u[i-1, j] + u[i+1, j] + u[i, j-1] + u[i, j+1] - 4 u[i, j] = L[i, j] on the interior, u = d on the region's outer ring
+      6. store    clip(rint(u), 0, 255) over the interior = the patch rectangle inset by 2.  ASSUMPTION (rounding): half to even, as
+                  np.rint and cv2's saturate_cast.  The ring, the patch's outermost line and the rest of the image keep their bytes.
+    Solved directly with the type-I sine transform (cremage_amd.ops.poisson_tables): with n = hp - 2, m = wp - 2 and F = L minus the ring
+    neighbours, u = S_n ((S_n F S_m) / ((lam_n + lam_m) (n+1)(m+1)/4)) S_m.  `dtype` float64 is the definition; float32 runs the same
+    code with fp32 tables and products - the yardstick of the device path's tolerance.  ASSUMPTION (arithmetic): cv2 solves in fp32
+    with its own transform; its bits are not reproduced.
+    A patch with h < 5 or w < 5 has no interior: the image comes back unchanged.  With an empty mask (hp <= 2 margin or wp <= 2 margin)
+    the exact solution is d itself; no shortcut is taken - the solve returns d to round-off (1e-9 at most here, a few 1e-3 in fp32
+    at the largest patches), which rint removes, so the image comes back unchanged as well.  Returns the uint8 image (a copy), and with return_field the solution before rounding as well,
+    `dtype` [h-4, w-4, c]."""
+    from .ops import poisson_tables
+    img, pat = np.asarray(image_u8_hwc), np.asarray(patch_u8_hwc)
+    if img.dtype != np.uint8 or pat.dtype != np.uint8 or img.ndim != 3 or pat.ndim != 3 or img.shape[2] != pat.shape[2]:
+        raise ValueError(f"poisson_clone_host: uint8 [H, W, c] image and [h, w, c] patch expected, got {img.dtype} {img.shape} and {pat.dtype} {pat.shape}")
+    x, y, margin = int(x), int(y), int(margin)
+    (h, w), (H, W) = pat.shape[:2], img.shape[:2]
+    if h < 1 or w < 1 or x < 0 or y < 0 or x + w > W or y + h > H:
+        raise ValueError(f"poisson_clone_host: patch {h}x{w} at (x {x}, y {y}) is empty or lies outside the {H}x{W} image")
+    if margin < 0:
+        raise ValueError(f"poisson_clone_host: margin must not be negative (got {margin})")
+    out = img.copy()
+    n, m = h - 4, w - 4
+    if n < 1 or m < 1:
+        field = np.zeros((max(n, 0), max(m, 0), img.shape[2]), dtype=dtype)
+    else:
+        d = img[y + 1:y + h - 1, x + 1:x + w - 1].astype(np.int64)
+        F = _poisson_rhs(d, pat[1:h - 1, 1:w - 1].astype(np.int64), margin).astype(dtype)
+        (sn, ln), (sm, lm) = poisson_tables(n), poisson_tables(m)
+        den = ((ln[:, None] + lm[None, :]) * ((n + 1) * (m + 1) / 4.0)).astype(dtype)
+        sn, sm = sn.astype(dtype), sm.astype(dtype)
+        field = np.empty(F.shape, dtype=dtype)
+        for c in range(F.shape[2]):
+            t = ((sn @ F[..., c]) @ sm) / den
+            field[..., c] = (sn @ t) @ sm
+        out[y + 2:y + h - 2, x + 2:x + w - 2] = np.clip(np.rint(field), 0, 255).astype(np.uint8)
+    return (out, field) if return_field else out
+
+
 def paste_face(image, face_image, plan: FaceCropPlan, mode: str = "paste"):
     """Put the updated face back.  mode "paste": `pil_image.paste(updated, (x, y))`, the form the reference keeps as a comment
     (face_detector_engine.py:269).  mode "seamless" is the reference's live path (cv.seamlessClone NORMAL_CLONE, :271-286): cv2 is not
-    installable here, so it is not restated."""
+    installable here, so a form pinned against it does not exist and the name raises.  mode "poisson": `poisson_clone_host` at
+    (plan.x, plan.y) - NORMAL_CLONE restated from the published algorithm, a stated approximation that is unpinned against cv2 (its
+    assumptions are listed there: erosion margin 3, inset of 1, rint rounding, float64 instead of cv2's fp32 arithmetic)."""
     if mode == "seamless":
         raise NotImplementedError("cv.seamlessClone (Poisson blending) needs OpenCV, which this build cannot import or pin against")
-    if mode != "paste":
+    if mode not in PASTE_MODES:
         raise ValueError(f"unknown paste mode {mode!r}")
+    if mode == "poisson":
+        from PIL import Image
+        a = np.asarray(image)
+        p = np.asarray(face_image.convert(image.mode))
+        if a.ndim == 2:
+            return Image.fromarray(poisson_clone_host(a[..., None], p[..., None], plan.x, plan.y)[..., 0])
+        return Image.fromarray(poisson_clone_host(a, p, plan.x, plan.y))
     out = image.copy()
     out.paste(face_image.convert(image.mode), (plan.x, plan.y))
     return out
@@ -132,7 +227,8 @@ def face_fix(image, faces: Iterable[Sequence[float]], img2img_fn: Callable[[torc
              paste_mode: str = "paste"):
     """The auto-face-fix loop of one image (face_detector_engine.py:332-360 `fix_engine`: `process_face` for every detected face in turn, each
     pass working on the image the previous pass produced).  `img2img_fn`: [1, 3, edge, edge] in [-1, 1] -> [1, 3, edge, edge] in [0, 1] - the UNet
-    re-entry (cremage_amd.pipeline.img2img / img2img_sdxl at the face-fix strength)."""
+    re-entry (cremage_amd.pipeline.img2img / img2img_sdxl at the face-fix strength).  `paste_mode`: as `paste_face`'s mode - "paste" (the
+    default) or "poisson", the gradient-domain blend."""
     for face in faces:
         plan = face_crop_plan(face, image.size, target_edge_len)
         square = crop_and_pad(image, plan)
@@ -206,21 +302,31 @@ def crop_and_pad_device(image: torch.Tensor, plan: FaceCropPlan) -> torch.Tensor
                            out_offset=(plan.pad_x, plan.pad_y), out_affine=(2.0, -1.0), fill=1.0)
 
 
-def unpad_resize_paste_device(working_u8: torch.Tensor, updated: torch.Tensor, plan: FaceCropPlan) -> torch.Tensor:
-    """`paste_face(image, unpad_and_resize(unit_tensor_to_pil(updated[0]), plan), plan)` on the device, IN PLACE: the inner box of
-    `updated` ([1, 3, edge, edge] fp32 in [0, 1]) is quantised, resized to the crop rectangle's size and written over that rectangle
-    of `working_u8` ([1, 3, H, W] uint8).  Nothing outside the rectangle is touched.  Returns working_u8."""
+def unpad_resize_paste_device(working_u8: torch.Tensor, updated: torch.Tensor, plan: FaceCropPlan, paste_mode: str = "paste") -> torch.Tensor:
+    """`paste_face(image, unpad_and_resize(unit_tensor_to_pil(updated[0]), plan), plan, paste_mode)` on the device, IN PLACE: the inner box
+    of `updated` ([1, 3, edge, edge] fp32 in [0, 1]) is quantised, resized to the crop rectangle's size and, with "paste", written over
+    that rectangle of `working_u8` ([1, 3, H, W] uint8); with "poisson" it goes to a temporary uint8 [1, 3, h, w] tensor that
+    cremage_amd.ops.poisson_clone blends in (fp32 solve: bytes within 1 of the host's).  Nothing outside the rectangle is touched.
+    Returns working_u8."""
     from . import ops
-    return ops.resample_u8(updated, (plan.h, plan.w), window=(plan.pad_x, plan.pad_y, plan.new_w, plan.new_h), out=working_u8,
-                           out_offset=(plan.x, plan.y))
+    if paste_mode == "seamless":
+        raise NotImplementedError("cv.seamlessClone (Poisson blending) needs OpenCV, which this build cannot import or pin against")
+    if paste_mode not in PASTE_MODES:
+        raise ValueError(f"unknown paste mode {paste_mode!r}")
+    window = (plan.pad_x, plan.pad_y, plan.new_w, plan.new_h)
+    if paste_mode == "poisson":
+        face = ops.resample_u8(updated, (plan.h, plan.w), window=window, out_dtype=torch.uint8)
+        return ops.poisson_clone(working_u8, face, (plan.x, plan.y), POISSON_MARGIN)
+    return ops.resample_u8(updated, (plan.h, plan.w), window=window, out=working_u8, out_offset=(plan.x, plan.y))
 
 
 def face_fix_device(image: torch.Tensor, faces: Iterable[Sequence[float]], img2img_fn: Callable[[torch.Tensor], torch.Tensor],
-                    target_edge_len: int = 512) -> torch.Tensor:
+                    target_edge_len: int = 512, paste_mode: str = "paste") -> torch.Tensor:
     """`face_fix` with the image staying on the device.  image: [3, H, W] fp32 in [0, 1] (quantised ONCE, as unit_tensor_to_pil does) or
     uint8; the working image is a device uint8 tensor, every face works on what the previous one left, and `img2img_fn` gets and
-    returns device tensors ([1, 3, edge, edge] in [-1, 1] -> in [0, 1]).  Plain paste only (see paste_face).  Returns the working image,
-    uint8 [3, H, W] on the device - the bytes of the PIL image face_fix returns."""
+    returns device tensors ([1, 3, edge, edge] in [-1, 1] -> in [0, 1]).  paste_mode as in paste_face ("paste", the default, or
+    "poisson").  Returns the working image, uint8 [3, H, W] on the device - with "paste" the bytes of the PIL image face_fix returns,
+    with "poisson" those bytes within 1."""
     if image.dim() != 3:
         raise ValueError(f"face_fix_device: [3, H, W] image expected, got {tuple(image.shape)}")
     if image.dtype == torch.uint8:
@@ -233,7 +339,7 @@ def face_fix_device(image: torch.Tensor, faces: Iterable[Sequence[float]], img2i
         out = img2img_fn(crop_and_pad_device(work, plan))
         if out.shape[-2:] != (plan.edge, plan.edge):
             raise ValueError(f"img2img returned {tuple(out.shape)} for a {plan.edge}x{plan.edge} input")
-        unpad_resize_paste_device(work, out[:1].float(), plan)
+        unpad_resize_paste_device(work, out[:1].float(), plan, paste_mode)
     return work[0]
 
 

@@ -518,6 +518,42 @@ typedef struct {
 } crg_resample_args;
 int crg_resample_u8(crg_ctx* ctx, void* stream, const crg_resample_args* args);
 
+/* Gradient-domain (Poisson) paste of a rectangle, IN PLACE on the device: OpenCV's seamlessClone NORMAL_CLONE as the reference calls
+ * it with an all-white mask (face_detector_engine.py:271-286), restated from the published algorithm and NOT pinned against cv2
+ * (cremage_amd.postprocess.poisson_clone_host is the definition and the fp64 yardstick).  Per image and channel, as real numbers:
+ *   region  d = image[y+1 .. y+h-2][x+1 .. x+w-2], s = patch[1 .. h-2][1 .. w-2]   (hp x wp = (h-2) x (w-2): the rectangle inset by 1)
+ *   mask    k[r][c] = 1 for margin <= r < hp - margin and margin <= c < wp - margin, else 0   (three 3x3 erosions: margin 3)
+ *   field   vx = k ? s[r][c+1] - s[r][c] : d[r][c+1] - d[r][c],  vy the same down the rows     (forward differences)
+ *   L[r][c] = vx[r][c] - vx[r][c-1] + vy[r][c] - vy[r-1][c]                                    for 1 <= r <= hp-2, 1 <= c <= wp-2
+ *   solve   u[r-1][c] + u[r+1][c] + u[r][c-1] + u[r][c+1] - 4 u[r][c] = L[r][c], u = d on the region's outer ring
+ *   store   image[y+2 .. y+h-3][x+2 .. x+w-3] = clip(rint(u), 0, 255), rint = half to even; nothing else is written
+ * Solved directly with the type-I sine transform on the n x m = (h-4) x (w-4) interior: F = L with the ring moved to the right-hand
+ * side, u = S_n ((S_n F S_m) * rden) S_m, S_k[a][b] = sin(pi (a+1)(b+1) / (k+1)), rden[a][b] = 4 / ((n+1)(m+1) (lam_n[a] + lam_m[b])),
+ * lam_k[a] = 2 cos(pi (a+1) / (k+1)) - 2.  Launches: one right-hand-side kernel (integer arithmetic, exact fp32 F) and four batched
+ * fp32 matrix products on v_mfma_f32_32x32x2_f32 (plain store; * rden; plain store; round / clip / uint8 store through the image's
+ * strides, and the fp32 field when `field` is not NULL).  M, N and K are ragged and guarded; nothing is padded in memory.
+ * image and patch are strided uint8 [N][3][rows][columns] tensors (strides in ELEMENTS = bytes: contiguous NCHW and channels-last
+ * alike) that must not overlap; the patch tensor is h x w.  s_rows = S_n [n][n], s_cols = S_m [m][m], rden [n][m]: host-built fp32
+ * DEVICE tables.  work: 2 * N * 3 * n * m floats.  field: contiguous fp32 [N][3][n][m] or NULL.  h >= 5 and w >= 5.
+ * No atomics, no host synchronisation, no allocation; two identical calls give identical bits. */
+typedef struct {
+  void* image;             /* [N][3][img_h][img_w] uint8, strided, written in place */
+  int64_t img_sn, img_sc, img_sy, img_sx;
+  int img_h, img_w;
+  const void* patch;       /* [N][3][h][w] uint8, strided */
+  int64_t pat_sn, pat_sc, pat_sy, pat_sx;
+  int N;
+  int h, w;                /* the patch */
+  int x, y;                /* its top-left corner in the image */
+  int margin;
+  const float* s_rows;     /* S_(h-4) */
+  const float* s_cols;     /* S_(w-4) */
+  const float* rden;       /* [h-4][w-4] */
+  float* work;             /* 2 * N * 3 * (h-4) * (w-4) floats */
+  float* field;            /* [N][3][h-4][w-4] or NULL */
+} crg_poisson_args;
+int crg_poisson_clone(crg_ctx* ctx, void* stream, const crg_poisson_args* args);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
