@@ -967,7 +967,12 @@ SCORE_BUDGET_BYTES = 256 << 20  # fp32 score buffer of the unfused attention pat
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_keys: int, scale: float) -> torch.Tensor:
     """softmax(Q K^T * scale) V with heads split along the channel dim.
-    q: [B, Nq, C], k: [B, Nk, C], vt: [B, C, ld] (V transposed, ld = roundup(Nk, 8)) -> [B, Nq, C]."""
+    q: [B, Nq, C], k: [B, Nk, C], vt: [B, C, ld] (V transposed, ld = roundup(Nk, 8)) -> [B, Nq, C].
+    Pad columns n_keys..ld of vt: the flash branch (half type, d_head <= 160) masks keys >= n_keys and never reads them unmasked, so
+    anything may sit there.  The unfused branch (fp32, or d_head > 160) does NOT mask: its PV GEMM runs over roundup(n_keys, 8)
+    columns and multiplies the pads by the score buffer's pad columns, which are exact zeros - finite pads drop out bitwise,
+    non-finite ones (NaN, inf) would poison every output.  Every producer in this module (`linear_transposed`, `linear` /
+    `ln_linear` with transposed_from) zeroes them; a caller that builds vt itself must do the same."""
     _need_cuda(q, k, vt)
     B, Nq, Cc = q.shape
     Dh = Cc // heads

@@ -1,13 +1,13 @@
 """The per-kernel parity suite against the fp16 build of the library (libcrg_hip_f16.so, CRG_HALF=f16).
 
-The library is chosen when cremage_amd is imported, so the fp16 run is ONE fresh child process: tests/test_hip_ops.py and
-tests/test_half_type_edges.py (both generic over the process's half type, fp16 bounds = bf16 bounds / 8) plus the two fp32-class VAE
-goldens of tests/test_hip_models.py, whose three-pass convs then run on fp16 planes.  The child's first test establishes that it
+The library is chosen when cremage_amd is imported, so the fp16 run is ONE fresh child process: tests/test_hip_ops.py,
+tests/test_half_type_edges.py and tests/test_batched_gemm_gpu.py (all generic over the process's half type, fp16 bounds = bf16
+bounds / 8) plus the two fp32-class VAE goldens of tests/test_hip_models.py, whose three-pass convs then run on fp16 planes.  The child's first test establishes that it
 really runs the fp16 library (test_half_type_edges.py::test_library_of_this_process_half_type).  test_linear_ring_gemm starts a
 grandchild that inherits CRG_HALF: at most three processes hold the GPU.
 
-Measured on MI355X: the child takes 35 s for its 393 cases (the whole `-m gpu` run: 107 s for 468 cases before this file, 152 s for
-519 with it and with tests/test_half_type_edges.py in the parent; the suite's limit is 900 s), so nothing is deselected; a
+Measured on MI355X: the child takes 37 s for its 438 cases, 1.2 s of them for the 45 of tests/test_batched_gemm_gpu.py (the whole
+`-m gpu` run: 164 s for 646 cases; the suite's limit is 900 s), so nothing is deselected; a
 parametrisation that had to be would be listed in DESELECT with its seconds, and the count below compares against the selection minus
 that list.
 
@@ -62,8 +62,15 @@ Largest fp16 figure seen per test function against its bound (MI355X; `pytest -r
   test_few_keys_kernel_large_logits                   rel-L2    9.02e-05 / 2.50e-03  (0.04)
   test_layernorm_epilogue_large_offset                rel-L2    6.97e-04 / 7.50e-04  (0.93)
   test_layernorm_two_pass_large_offset                rel-L2    2.09e-04 / 7.50e-04  (0.28)
+  test_raw_batched_gemm                               rel-L2    2.10e-04 / 7.50e-04  (0.28)
+  test_linear_transposed_batched                      rel-L2    2.08e-04 / 7.50e-04  (0.28)
+  test_unfused_attention_batched                      rel-L2    1.58e-05 / 5.00e-05  (0.32)
+  test_unfused_attention_finite_garbage_in_v_pads     rel-L2    2.65e-04 / 1.25e-03  (0.21)
+  test_softmax_rows_strided                           rel-L2    1.90e-04 / 7.50e-04  (0.25)
 fp16 subnormals survive the conversions, the LDS-DMA path and the _f16 matrix instructions (fp32-class and crowd-attention rows:
-at the 'subnormals kept' emulation, 20x to 200x below the 'flushed' one).  The one finding: test_layernorm_epilogue_large_offset
+at the 'subnormals kept' emulation, 20x to 200x below the 'flushed' one).  test_unfused_attention_batched's largest figure is the
+fp32-class attention over 1536 keys (6.7e-6 on bf16 planes): probabilities near 1 / 1536 sit at the bottom of fp16's normal range, where
+the lo plane of P has only subnormal steps left.  The one finding: test_layernorm_epilogue_large_offset
 (GEGLU, offset 100 sigma) was at 9.8e-4 before the fp16 build folded the row statistics in fp64 (gemm_shared.h ln_row_coeffs).
 """
 import os
@@ -75,10 +82,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SELECTION = ["tests/test_hip_ops.py", "tests/test_half_type_edges.py",
+SELECTION = ["tests/test_hip_ops.py", "tests/test_half_type_edges.py", "tests/test_batched_gemm_gpu.py",
              "tests/test_hip_models.py::test_vae_sd15_full_decode_pixels", "tests/test_hip_models.py::test_vae_sd15_full_encode"]
 DESELECT = []  # node ids (individual parametrisations only), each with its measured seconds
-CHILD_TIME_LIMIT = 90  # seconds: about twice the measured 35
+CHILD_TIME_LIMIT = 80  # seconds: about twice the measured 37
 
 
 def _pytest(extra, timeout):
@@ -95,7 +102,7 @@ def test_op_suite_against_the_fp16_library():
     m = re.search(r"^(\d+)(?:/\d+)? tests? collected", c.stdout, re.M)
     assert c.returncode == 0 and m, c.stdout[-3000:] + c.stderr[-3000:]
     collected = int(m.group(1))
-    assert collected >= 341 + 2
+    assert collected >= 341 + 2 + 45  # + tests/test_batched_gemm_gpu.py
     r = _pytest(["-rs"], CHILD_TIME_LIMIT)  # started once: a failure is shown, not retried
     tail = r.stdout[-6000:] + r.stderr[-3000:]
     assert r.returncode == 0, tail
