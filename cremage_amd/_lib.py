@@ -144,6 +144,19 @@ class PoissonArgs(C.Structure):
     ]
 
 
+class BlendArgs(C.Structure):
+    _fields_ = [
+        ("original", c_void_p), ("org_sn", c_int64), ("org_sy", c_int64), ("org_sx", c_int64),
+        ("updated", c_void_p), ("upd_sn", c_int64), ("upd_sy", c_int64), ("upd_sx", c_int64),
+        ("mask", c_void_p), ("msk_sn", c_int64), ("msk_sy", c_int64), ("msk_sx", c_int64),
+        ("gray_mode", c_int),
+        ("out", c_void_p), ("out_sn", c_int64), ("out_sy", c_int64), ("out_sx", c_int64),
+        ("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int),
+        ("win_x", c_int), ("win_y", c_int), ("win_w", c_int), ("win_h", c_int),
+        ("taps", C.c_double * 11),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -203,6 +216,7 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_float, c_float, c_float]),
     "crg_resample_u8": (c_int, [c_void_p, c_void_p, C.POINTER(ResampleArgs)]),
     "crg_poisson_clone": (c_int, [c_void_p, c_void_p, C.POINTER(PoissonArgs)]),
+    "crg_blur_blend_u8": (c_int, [c_void_p, c_void_p, C.POINTER(BlendArgs)]),
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),

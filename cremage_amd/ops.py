@@ -1476,6 +1476,68 @@ def poisson_clone(image_u8: torch.Tensor, patch_u8: torch.Tensor, offset: Tuple[
     return _written(image_u8)
 
 
+# ---------------------------------------------------------------------------------- blurred-mask composite
+BLEND_GRAY = {"channel": 0, "cv_rgb": 1}
+
+
+def blur_blend_u8(original: torch.Tensor, updated: torch.Tensor, mask: torch.Tensor, *, gray: str = "channel",
+                  out: Optional[torch.Tensor] = None, window: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+    """postprocess.blend_blurred_mask on the device, one launch (crg_blur_blend_u8), equal to its bytes: the mask's grey level
+    blurred with cv2's 11 x 11 Gaussian (float64, reflect-101) weights `updated` over `original` (fp32, truncated).
+    original / updated: uint8 [H, W, C] or [N, H, W, C], C in 1..4, the channels adjacent - views are fine (a window of a larger
+    image, the first three channels of an RGBA image).  mask: uint8; gray "channel": [H, W] or [N, H, W] (or a last dimension of 1),
+    "cv_rgb": [..., 3 or 4] through cv2's RGB -> GRAY.  A mask without the batch dimension serves every image.  `out`: like
+    `original`; it may BE `original` (in place), otherwise it must not overlap any input; default a new contiguous tensor.
+    `window` = (x, y, w, h): the caller's statement that the mask is 0 outside this rectangle inset by 5 (postprocess.mask_window);
+    tiles outside it skip the blur and the bytes are those of the run without it.  H, W >= 6.  Returns `out`."""
+    _need_cuda(original, updated, mask, out)
+    if gray not in BLEND_GRAY:
+        raise L.CrgError(f"blur_blend_u8: unknown gray {gray!r} (one of {list(BLEND_GRAY)})")
+    if original.dtype != torch.uint8 or updated.dtype != torch.uint8 or mask.dtype != torch.uint8 or (out is not None and out.dtype != torch.uint8):
+        raise L.CrgError("blur_blend_u8: uint8 tensors expected")
+    if original.dim() not in (3, 4) or updated.shape != original.shape:
+        raise L.CrgError(f"blur_blend_u8: [H, W, C] or [N, H, W, C] images of one shape expected, got {tuple(original.shape)} and {tuple(updated.shape)}")
+    batched = original.dim() == 4
+    n, (H, W, ch) = (original.shape[0] if batched else 1), original.shape[-3:]
+    if out is None:
+        out = torch.empty(tuple(original.shape), dtype=torch.uint8, device=original.device)
+    elif out.shape != original.shape:
+        raise L.CrgError(f"blur_blend_u8: out of shape {tuple(original.shape)} expected, got {tuple(out.shape)}")
+    if gray == "channel" and mask.dim() >= 2 and tuple(mask.shape[-2:]) == (H, W) and mask.dim() in (2, 3 if batched else 2):
+        mask = mask[..., None]
+    mch = (1,) if gray == "channel" else (3, 4)
+    if mask.dim() not in (3, 4 if batched else 3) or tuple(mask.shape[-3:-1]) != (H, W) or mask.shape[-1] not in mch or \
+            (mask.dim() == 4 and mask.shape[0] != n):
+        raise L.CrgError(f"blur_blend_u8: the mask {tuple(mask.shape)} does not fit {tuple(original.shape)} images with gray={gray!r}")
+    for t in (original, updated, out, mask):
+        if t.device != original.device:
+            raise L.CrgError(f"blur_blend_u8: tensors on {original.device} and {t.device}")
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise L.CrgError("blur_blend_u8: the channels of a pixel must be adjacent")
+    if n < 1 or ch < 1 or ch > 4 or H < 6 or W < 6:
+        raise L.CrgError(f"blur_blend_u8: {n} images of {H}x{W}x{ch}: 1..4 channels and at least 6x6 pixels are needed")
+    a = L.BlendArgs()
+
+    def strides(t, with_n):
+        return (t.stride(0) if with_n else 0, t.stride(-3), t.stride(-2))
+    a.original, (a.org_sn, a.org_sy, a.org_sx) = original.data_ptr(), strides(original, batched)
+    a.updated, (a.upd_sn, a.upd_sy, a.upd_sx) = updated.data_ptr(), strides(updated, batched)
+    a.mask, (a.msk_sn, a.msk_sy, a.msk_sx) = mask.data_ptr(), strides(mask, mask.dim() == 4)
+    a.out, (a.out_sn, a.out_sy, a.out_sx) = out.data_ptr(), strides(out, batched)
+    if any(v < 0 for v in (a.org_sn, a.upd_sn, a.msk_sn, a.out_sn)) or (batched and n > 1 and a.out_sn == 0):
+        raise L.CrgError("blur_blend_u8: batch strides must not be negative (out: positive)")
+    a.gray_mode, a.N, a.H, a.W, a.C = BLEND_GRAY[gray], n, H, W, ch
+    if window is not None:
+        a.win_x, a.win_y, a.win_w, a.win_h = (int(v) for v in window)
+        if a.win_w < 1 or a.win_h < 1:
+            raise L.CrgError(f"blur_blend_u8: empty window {tuple(window)}")
+    from .postprocess import gaussian_taps_11
+    a.taps[:] = [float(v) for v in gaussian_taps_11()]
+    hd = _h(original)
+    L.check(L.load().crg_blur_blend_u8(hd, _st(), C.byref(a)), hd, "crg_blur_blend_u8")
+    return _written(out)
+
+
 # ---------------------------------------------------------------------------------- profiling
 class profile:
     """Context manager: per-kernel device time (HIP events on the launch stream) + algorithmic FLOPs/bytes of

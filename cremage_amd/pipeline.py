@@ -598,3 +598,118 @@ def face_fix_sd15(ldm: LatentDiffusion, images: torch.Tensor, faces, c: torch.Te
             return y
         out.append(_face_fix_one(PP, images[i], faces[i], i2i, target_edge_len, resample, paste_mode))
     return torch.stack(out).to(images.device)
+
+
+# ---------------------------------------------------------------------------------------------- spot inpainting (tools/spot_inpainter.py)
+GLUES = ("host", "device")  # where the pixel steps around the inpainting UNet run: PIL / numpy on the host, or the HIP twins
+
+
+def _glue(name: str) -> str:
+    if name not in GLUES:
+        raise ValueError(f"unknown glue {name!r} (one of {list(GLUES)})")
+    return name
+
+
+def _u8_hwc_device(image, device, channels: bool) -> torch.Tensor:
+    """PIL image or uint8 tensor -> device uint8 [H, W, 3] (channels) or [H, W] (grey, PIL's "L")"""
+    if not torch.is_tensor(image):
+        image = torch.from_numpy(np.array(image.convert("RGB" if channels else "L")))
+    if image.dtype != torch.uint8 or image.dim() != (3 if channels else 2):
+        raise ValueError(f"uint8 {'[H, W, C]' if channels else '[H, W]'} tensor expected, got {image.dtype} {tuple(image.shape)}")
+    return image.to(device)
+
+
+@torch.no_grad()
+def inpaint_image(ldm: LatentDiffusion, image, mask, c: torch.Tensor, uc: Optional[torch.Tensor], *, width: int, height: int, steps: int = 50,
+                  cfg_scale: float = 7.5, eta: float = 1.0, seed: Optional[int] = None, glue: str = "host",
+                  noise_sampler: Optional[Callable] = None, enc_noise: Optional[torch.Tensor] = None):
+    """One image through the reference's inpainting generate call (inpaint.py:110-147 and :357-399 around `inpaint`): the image and
+    the mask (white = repaint) are resized and white-padded to (width, height) rounded up to multiples of 64 when their size differs
+    from it (postprocess.resize_with_padding - the padding of the mask is white too), make_batch_sd, the 9-channel UNet under DDIM,
+    the blurred-mask composite over the padded original and the crop to the padding's inner box.  c / uc: one conditioning row.
+    glue "host" (the default): PIL images in, PIL RGB image out, the pixel steps in PIL / numpy.  glue "device": the image (PIL, or
+    uint8 [H, W, 3 or 4] tensor) and the mask (PIL, read as "L", or uint8 [H, W]) go to the device once and stay there - two launches
+    of ops.resample_u8 for the padding, ops.blur_blend_u8 for the composite - and the result is a device uint8 [h, w, 3] tensor with
+    the host arm's bytes.  The device arm reads channels 0-2 of the image and a GREY mask: PIL premultiplies a non-opaque alpha
+    before it resizes, which is not restated."""
+    from . import postprocess as PP
+    glue = _glue(glue)
+    dev = ldm.device
+    pw, ph = PP.bbox_for_multiple_of_64(width, height)
+    kw = dict(steps=steps, cfg_scale=cfg_scale, eta=eta, seed=seed, noise_sampler=noise_sampler, enc_noise=enc_noise)
+    if glue == "host":
+        bbox = None
+        if image.size != (pw, ph):
+            image, bbox = PP.resize_with_padding(image, pw, ph)
+        if mask.size != (pw, ph):
+            mask, _ = PP.resize_with_padding(mask, pw, ph)
+        img, m, _ = PP.inpaint_batch(image, mask)
+        out, _ = inpaint(ldm, img.to(dev), m.to(dev), c, uc, **kw)
+        return PP.composite_inpaint(image, PP.unit_tensor_to_pil(out[0]), mask, bbox)
+    orig = _u8_hwc_device(image, dev, True)[..., :3]
+    grey = _u8_hwc_device(mask, dev, False)
+    bbox = None
+    if (orig.shape[1], orig.shape[0]) != (pw, ph):
+        nw, nh, px, py = PP.resize_with_padding_plan(orig.shape[1], orig.shape[0], pw, ph)
+        padded = torch.empty((ph, pw, 3), dtype=torch.uint8, device=dev)
+        ops.resample_u8(orig.permute(2, 0, 1)[None], (nh, nw), out=padded.permute(2, 0, 1)[None], out_offset=(px, py), fill=255.0)
+        orig, bbox = padded, (px, py, px + nw, py + nh)
+    if (grey.shape[1], grey.shape[0]) != (pw, ph):
+        nw, nh, px, py = PP.resize_with_padding_plan(grey.shape[1], grey.shape[0], pw, ph)
+        padded = torch.empty((ph, pw), dtype=torch.uint8, device=dev)
+        ops.resample_u8(grey[None, None], (nh, nw), out=padded[None, None], out_offset=(px, py), fill=255.0)
+        grey = padded
+    img = PP.u8_to_unit_device(orig.permute(2, 0, 1)[None], (2.0, -1.0))  # v / 127.5 - 1 to the bit: 2 (v / 255) is exact
+    m = (grey >= 128).to(torch.float32)[None, None]                        # float32(v) / 255 >= 0.5
+    out, _ = inpaint(ldm, img, m, c, uc, **kw)
+    inpainted = (255.0 * out[0].clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous()
+    return PP.composite_inpaint_device(orig, inpainted, grey, bbox)
+
+
+@torch.no_grad()
+def spot_fix_sd15(ldm: LatentDiffusion, image: torch.Tensor, mask, c: torch.Tensor, uc: Optional[torch.Tensor], *, steps: int = 20,
+                  strength: float = 0.5, cfg_scale: float = 7.5, resample: str = "host", boxes=None, target_edge_len: int = 512,
+                  enc_noise: Optional[torch.Tensor] = None, fwd_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Spot inpainting with a regular SD1.5 model (spot_inpainter.py "Apply inpainting" without the inpainting checkbox): every
+    connected region of the mask gets one `img2img` pass (DDIM, strength 0.5 - the tool's default -, batch 1) through the face-fix
+    geometry, and the whole image is blended through the blurred mask after each (postprocess.spot_fix).  image: [3, H, W] in [0, 1]
+    on the model's device; mask: HOST uint8 [H, W] (array or tensor; > 127 = repaint); c / uc: [1, 77*n, 768]; `boxes`: (x, y, w, h)
+    boxes to use instead of postprocess.mask_boxes(mask) - their order and connectivity are assumptions about cv2 stated there.
+    `resample` ("host", the default, or "device"): "device" keeps the image on the GPU between the boxes
+    (postprocess.spot_fix_device) and returns the same tensor to the bit.  Returns [3, H, W] in [0, 1] on the image's device."""
+    from . import postprocess as PP
+    resample = _resampler(resample)
+    mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
+
+    def i2i(x):
+        y, _ = img2img(ldm, x.to(image.device), c, uc, steps=steps, strength=strength, cfg_scale=cfg_scale, enc_noise=enc_noise, fwd_noise=fwd_noise)
+        return y
+    if resample == "device":
+        u8 = PP.spot_fix_device(image, mask, i2i, boxes, target_edge_len)
+        return (PP.u8_to_unit_device(u8[None], (2.0, -1.0))[0] + 1.0) * 0.5
+    pil = PP.spot_fix(PP.unit_tensor_to_pil(image), mask, i2i, boxes, target_edge_len)
+    return ((PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5).to(image.device)
+
+
+@torch.no_grad()
+def spot_inpaint_sd15(inpaint_ldm: LatentDiffusion, image: torch.Tensor, mask, c: torch.Tensor, uc: Optional[torch.Tensor], *,
+                      max_edge_len: int = 768, steps: int = 50, cfg_scale: float = 7.5, eta: float = 1.0, seed: Optional[int] = None,
+                      glue: str = "host", noise_sampler: Optional[Callable] = None, enc_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Spot inpainting with the SD1.5 inpainting model (the tool's inpainting checkbox): the window of at most max_edge_len squared
+    around every mask region (postprocess.mask_single_box / spot_window) goes through `inpaint_image` at width = height =
+    max_edge_len and the patch is pasted at the window's origin (postprocess.spot_inpaint, whose oversize-patch quirk is kept).
+    image: [3, H, W] in [0, 1] on the model's device; mask: HOST uint8 [H, W].  `glue` "device" keeps every pixel step on the GPU
+    (postprocess.spot_inpaint_device, inpaint_image's device arm) and returns the same tensor to the bit.  Returns [3, H, W] in [0, 1]."""
+    from . import postprocess as PP
+    glue = _glue(glue)
+    mask = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
+
+    def fn(crop, mask_crop, edge_len):
+        return inpaint_image(inpaint_ldm, crop, mask_crop, c, uc, width=edge_len, height=edge_len, steps=steps, cfg_scale=cfg_scale, eta=eta,
+                             seed=seed, glue=glue, noise_sampler=noise_sampler, enc_noise=enc_noise)
+    if glue == "device":
+        u8 = (255.0 * image.detach().float().clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous()
+        u8 = PP.spot_inpaint_device(u8, mask, fn, max_edge_len)
+        return (PP.u8_to_unit_device(u8.permute(2, 0, 1)[None], (2.0, -1.0))[0] + 1.0) * 0.5
+    pil = PP.spot_inpaint(PP.unit_tensor_to_pil(image), mask, fn, max_edge_len)
+    return ((PP.pil_to_unit_tensor(pil)[0] + 1.0) * 0.5).to(image.device)

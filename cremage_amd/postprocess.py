@@ -25,6 +25,11 @@ that a Cremage user finds the whole second-pass chain:
                                    (:357-398, use_seamless_clone = False): 11x11 Gaussian blur of the mask, alpha blend over the
                                    original, crop of the padding.  The blur is restated in numpy (see `gaussian_blur_11`).
 
+  spot inpainting                  tools/spot_inpainter.py: mask -> boxes (image_utils.py:314-393, restated without cv2: `mask_boxes`), the
+                                   window rule (:803-851), the per-box img2img flow (`spot_fix`) and the inpainting-model flow
+                                   (`spot_inpaint`), both ending in the blurred-mask blend (`blend_blurred_mask`; on the device
+                                   cremage_amd.ops.blur_blend_u8, the same bytes).
+
 Pure Python + PIL + numpy; nothing above the "device twins" section touches the HIP library.
 
 Device twins (`resample_u8_host` and the `*_device` functions): the same arithmetic with the image staying on the GPU.  PIL resizes
@@ -40,7 +45,7 @@ import json
 import os
 import time
 from dataclasses import dataclass
-from typing import Callable, Dict, Iterable, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -419,6 +424,266 @@ def composite_inpaint(original, inpainted, mask, bbox: Optional[Tuple[int, int, 
     out = inp * m[..., None] + orig * (np.float32(1.0) - m)[..., None]
     img = Image.fromarray(np.clip(out, 0, 255).astype(np.uint8))
     return img.crop(bbox) if bbox is not None else img
+
+
+# ---------------------------------------------------------------------------------------------- spot inpainting
+def _label_runs(binary: np.ndarray, diagonal: bool):
+    """Connected components of the True pixels of a [H, W] bool array by row runs and union-find: 8-connected with `diagonal`, else
+    4-connected.  Returns (row, start, end (exclusive), root) arrays, one entry per run, runs in raster order; `root` is the index of a
+    run of the same component (its representative)."""
+    H = binary.shape[0]
+    z = np.zeros((H, 1), dtype=np.int8)
+    d = np.diff(np.concatenate([z, binary.astype(np.int8), z], axis=1), axis=1)
+    rows, starts = np.nonzero(d == 1)  # row-major, so starts and ends pair up in order
+    ends = np.nonzero(d == -1)[1]
+    parent = list(range(len(rows)))
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    first = np.searchsorted(rows, np.arange(H + 1))  # runs of row y: first[y] .. first[y + 1]
+    slack = 1 if diagonal else 0
+    s, e = starts.tolist(), ends.tolist()
+    for y in range(1, H):
+        i, i_end, j, j_end = int(first[y - 1]), int(first[y]), int(first[y]), int(first[y + 1])
+        while i < i_end and j < j_end:
+            if s[i] < e[j] + slack and e[i] > s[j] - slack:
+                a, b = find(i), find(j)
+                if a != b:
+                    parent[max(a, b)] = min(a, b)
+            if e[i] < e[j]:
+                i += 1
+            else:
+                j += 1
+    return rows, starts, ends, np.array([find(i) for i in range(len(rows))], dtype=np.int64), first
+
+
+def mask_boxes(gray_u8: np.ndarray, order: str = "cv") -> List[Tuple[int, int, int, int]]:
+    """get_bounding_boxes_from_grayscale_image (image_utils.py:365-393) without cv2: threshold `> 127`, the 8-connected foreground
+    components, one tight box (x, y, w, h) per component - x the minimum column, w = maximum - minimum + 1 - and no box for a
+    component that lies inside a hole of another one (cv.RETR_EXTERNAL).  A component is outside every hole exactly when the
+    background above its first pixel is 4-connected to the image's frame.
+    cv2 cannot be imported here, so two points are stated ASSUMPTIONS that are not pinned against it:
+      (a) cv.findContours traces the 8-connected foreground (two blobs that touch at a diagonal pixel are one contour);
+      (b) its external contours come out in REVERSE raster order of each component's first pixel (top-most row, then left-most
+          pixel): the bottom component first.  order "cv" (the default) is that order, "raster" the forward one.
+    The order matters to spot_fix, where every box works on what the previous one left."""
+    if order not in ("cv", "raster"):
+        raise ValueError(f"unknown box order {order!r} (one of ['cv', 'raster'])")
+    a = np.asarray(gray_u8)
+    if a.ndim != 2:
+        raise ValueError(f"mask_boxes: a rank-2 grey image expected, got shape {a.shape}")
+    fg = a > 127
+    rows, starts, ends, root, _ = _label_runs(fg, True)
+    if len(rows) == 0:
+        return []
+    # the background of the image padded by one pixel, 4-connected: run 0 starts at the padded (0, 0) and is the outside
+    brows, bstarts, _, broot, bfirst = _label_runs(~np.pad(fg, 1), False)
+    boxes = []
+    for r in np.unique(root):  # ascending representative = raster order of the first pixel (runs are in raster order)
+        sel = root == r
+        y0, x0 = int(rows[r]), int(starts[r])  # the component's first pixel; padded (y0, x0 + 1) is the background above it
+        k = int(bfirst[y0]) + int(np.searchsorted(bstarts[bfirst[y0]:bfirst[y0 + 1]], x0 + 1, side="right")) - 1
+        if broot[k] != broot[0]:
+            continue  # inside a hole
+        xmin, xmax = int(starts[sel].min()), int(ends[sel].max()) - 1
+        ymin, ymax = int(rows[sel].min()), int(rows[sel].max())
+        boxes.append((xmin, ymin, xmax - xmin + 1, ymax - ymin + 1))
+    return boxes[::-1] if order == "cv" else boxes
+
+
+def mask_single_box(gray_u8: np.ndarray) -> Optional[Tuple[int, int, int, int]]:
+    """get_single_bounding_box_from_grayscale_image (image_utils.py:314-362): the union (x, y, w, h) of mask_boxes' boxes, None when
+    there are none."""
+    boxes = mask_boxes(gray_u8, "raster")
+    if not boxes:
+        return None
+    x0, y0 = min(b[0] for b in boxes), min(b[1] for b in boxes)
+    return (x0, y0, max(b[0] + b[2] for b in boxes) - x0, max(b[1] + b[3] for b in boxes) - y0)
+
+
+def spot_window(box: Sequence[int], image_size: Tuple[int, int], max_edge_len: int = 768) -> Tuple[int, int, int, int]:
+    """The window the inpainting model works on (spot_inpainter.py:803-851): the mask's box (x, y, w, h) grown to at most
+    max_edge_len x max_edge_len inside the image (image_size = PIL size (width, height)).  An image of exactly max_edge_len squared is
+    taken whole.  Otherwise the near edge moves out by half the spare length (int() of x - pad / 2, clamped to 0), the far edge is the
+    near edge + max_edge_len clamped to the image, and a second pass pulls the near edge back from the far edge, which uses the room
+    on the left / top when the box sits at the right / bottom border.  Raises ValueError for a box larger than max_edge_len."""
+    x, y, w, h = (int(v) for v in box)
+    edge = int(max_edge_len)
+    if w > edge or h > edge:
+        raise ValueError(f"masked region is width {w}, height {h}, which exceeds the maximum of {edge} x {edge}")
+    pil_w, pil_h = int(image_size[0]), int(image_size[1])
+    if pil_w == edge and pil_h == edge:
+        return (0, 0, edge, edge)
+    x = max(int(x - (edge - w) / 2), 0)
+    y = max(int(y - (edge - h) / 2), 0)
+    x2 = min(x + edge, pil_w)
+    y2 = min(y + edge, pil_h)
+    x = max(x2 - edge, 0)
+    y = max(y2 - edge, 0)
+    return (x, y, x2 - x, y2 - y)
+
+
+def gaussian_taps_11() -> np.ndarray:
+    """The eleven normalised float64 taps of gaussian_blur_11 (sigma 2), computed by the same expressions: what crg_blur_blend_u8 gets."""
+    k = np.exp(-((np.arange(11) - 5.0) ** 2) / (2.0 * 2.0 ** 2))
+    k /= k.sum()
+    return k
+
+
+def blend_blurred_mask(original_u8_hwc: np.ndarray, updated_u8_hwc: np.ndarray, gray_u8: np.ndarray) -> np.ndarray:
+    """The arithmetic shared by spot_inpainter.py:1021-1039 and inpaint.py:373-392 (composite_inpaint): the grey mask blurred with
+    gaussian_blur_11, as float32 / float32(255), is the weight m of `updated` over `original`; updated * m + original * (1 - m) in
+    float32 with every operation rounded on its own, clipped to [0, 255] and truncated to uint8.  uint8 [H, W, C] images and an uint8
+    [H, W] mask -> uint8 [H, W, C].  The definition of crg_blur_blend_u8 (cremage_amd.ops.blur_blend_u8), which returns these bytes."""
+    orig, upd, g = np.asarray(original_u8_hwc), np.asarray(updated_u8_hwc), np.asarray(gray_u8)
+    if orig.dtype != np.uint8 or upd.dtype != np.uint8 or g.dtype != np.uint8 or orig.ndim != 3 or orig.shape != upd.shape or g.shape != orig.shape[:2]:
+        raise ValueError(f"blend_blurred_mask: uint8 [H, W, C] images and an uint8 [H, W] mask expected, got {orig.dtype} {orig.shape}, "
+                         f"{upd.dtype} {upd.shape} and {g.dtype} {g.shape}")
+    m = gaussian_blur_11(g).astype(np.float32) / np.float32(255.0)
+    out = upd.astype(np.float32) * m[..., None] + orig.astype(np.float32) * (np.float32(1.0) - m)[..., None]
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def mask_window(gray_u8: np.ndarray) -> Optional[Tuple[int, int, int, int]]:
+    """(x, y, w, h): the bounding box of the non-zero grey levels grown by the blur's radius of 5 and clamped to the image - outside
+    it the blurred mask is 0 and blend_blurred_mask returns the original bytes.  None for an all-zero mask."""
+    g = np.asarray(gray_u8)
+    ys, xs = np.nonzero(g.any(axis=1))[0], np.nonzero(g.any(axis=0))[0]
+    if len(ys) == 0:
+        return None
+    x0, y0 = max(int(xs[0]) - 5, 0), max(int(ys[0]) - 5, 0)
+    return (x0, y0, min(int(xs[-1]) + 6, g.shape[1]) - x0, min(int(ys[-1]) + 6, g.shape[0]) - y0)
+
+
+def spot_fix(image, mask_gray_u8: np.ndarray, img2img_fn: Callable[[torch.Tensor], torch.Tensor], boxes=None, target_edge_len: int = 512):
+    """Spot inpainting with a regular model (spot_inpainter.py:867-888 and `process_box` :931-1046): one pass per box of the mask
+    (`boxes` defaults to mask_boxes(mask)), in order, each on what the previous one left.  A pass is the face-fix geometry - buffer 20,
+    clamp, Lanczos resize onto a white target_edge_len square (face_crop_plan / crop_and_pad), `img2img_fn` ([1, 3, edge, edge] in
+    [-1, 1] -> [0, 1]), un-pad, resize back, paste at (x, y) - followed by blend_blurred_mask over the WHOLE image against the image
+    as it was before this pass, with the FULL mask (not the box's part), as the reference does.  PIL image in, PIL RGB image out."""
+    from PIL import Image
+    mask = np.asarray(mask_gray_u8)
+    image = image.convert("RGB")
+    for box in (mask_boxes(mask) if boxes is None else boxes):
+        plan = face_crop_plan(box, image.size, target_edge_len)
+        out = img2img_fn(pil_to_unit_tensor(crop_and_pad(image, plan)))
+        if out.shape[-2:] != (plan.edge, plan.edge):
+            raise ValueError(f"img2img returned {tuple(out.shape)} for a {plan.edge}x{plan.edge} input")
+        pasted = image.copy()
+        pasted.paste(unpad_and_resize(unit_tensor_to_pil(out[0]), plan), (plan.x, plan.y))
+        image = Image.fromarray(blend_blurred_mask(np.asarray(image), np.asarray(pasted), mask))
+    return image
+
+
+def spot_inpaint(image, mask_gray_u8: np.ndarray, inpaint_fn: Callable, max_edge_len: int = 768):
+    """Spot inpainting with an inpainting model (spot_inpainter.py:791-852 and `process_box_for_inpainting` :1049-1126): the one box
+    around every mask region (mask_single_box) grown to the window of spot_window; the window of the image (as RGBA) and of the mask
+    go to `inpaint_fn(crop, mask_crop, edge_len=max_edge_len)`, which returns the composited, un-padded patch (PIL image or uint8
+    [h, w, 3] array: pipeline.inpaint_image), and the patch is pasted at the window's origin.  Without a mask region the image comes
+    back unchanged (the tool shows an alert and does nothing).
+    QUIRK kept from the reference: when the window is smaller than max_edge_len in both directions, the generate call scales the crop
+    UP to the padded size (inpaint.py:110-147), so the patch is LARGER than the window; it is pasted as it is and PIL clips it at the
+    image's border.  PIL image in, PIL image out."""
+    from PIL import Image
+    mask = np.asarray(mask_gray_u8)
+    box = mask_single_box(mask)
+    if box is None:
+        return image.copy()
+    x, y, w, h = spot_window(box, image.size, max_edge_len)
+    rect = (x, y, x + w, y + h)
+    patch = inpaint_fn(image.crop(rect).convert("RGBA"), Image.fromarray(mask).crop(rect), edge_len=max_edge_len)
+    if not isinstance(patch, Image.Image):
+        patch = Image.fromarray(np.asarray(patch))
+    out = image.copy()
+    out.paste(patch, (x, y))  # not resized to the window: see QUIRK
+    return out
+
+
+def resize_with_padding_plan(width: int, height: int, target_width: int, target_height: int) -> Tuple[int, int, int, int]:
+    """(new_w, new_h, pad_x, pad_y) of resize_with_padding for a width x height image: the geometry alone, for the device twin."""
+    new_h = int(height * (target_width / width))
+    if new_h > target_height:
+        new_w, new_h = int(width * (target_height / height)), target_height
+        pad_w = target_width - new_w
+        return new_w, new_h, int(pad_w / 2) + pad_w % 2, 0
+    pad_h = target_height - new_h
+    return target_width, new_h, 0, int(pad_h / 2) + pad_h % 2
+
+
+# device twins of the spot flows.  Images are device uint8 [H, W, C] tensors (PIL's layout) here; ops.resample_u8 takes their
+# [1, C, H, W] permuted views.
+def blend_blurred_mask_device(original: torch.Tensor, updated: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None,
+                              window: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+    """`blend_blurred_mask` on the device, one launch (cremage_amd.ops.blur_blend_u8), the same bytes.  original / updated: uint8
+    [H, W, C]; mask: uint8 [H, W]; `out` may be `original`; `window`: mask_window(mask) when the caller has the mask on the host."""
+    from . import ops
+    return ops.blur_blend_u8(original, updated, mask, gray="channel", out=out, window=window)
+
+
+def composite_inpaint_device(original: torch.Tensor, inpainted: torch.Tensor, mask: torch.Tensor,
+                             bbox: Optional[Tuple[int, int, int, int]] = None, window: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+    """`composite_inpaint` on the device: original (uint8 [H, W, 3 or 4], channels 0-2 are used), inpainted (uint8 [H, W, 3]) and the
+    mask - uint8 [H, W] grey, or [H, W, 3 or 4] through cv2's RGB -> GRAY - give the uint8 [H, W, 3] composite, cropped to `bbox`
+    = (x1, y1, x2, y2) (a view).  The bytes of np.asarray(composite_inpaint(...))."""
+    from . import ops
+    out = ops.blur_blend_u8(original[..., :3], inpainted[..., :3], mask, gray="channel" if mask.dim() == 2 else "cv_rgb", window=window)
+    return out[bbox[1]:bbox[3], bbox[0]:bbox[2]] if bbox is not None else out
+
+
+def spot_fix_device(image: torch.Tensor, mask_gray_u8: np.ndarray, img2img_fn: Callable[[torch.Tensor], torch.Tensor], boxes=None,
+                    target_edge_len: int = 512) -> torch.Tensor:
+    """`spot_fix` with the image staying on the device.  image: [3, H, W] fp32 in [0, 1] (quantised ONCE, as unit_tensor_to_pil does) or
+    uint8; mask: the HOST uint8 [H, W] array (the boxes come from it) - it is uploaded once.  Per box: crop_and_pad_device,
+    `img2img_fn` on device tensors, unpad_resize_paste_device ("paste") into a copy of the working image, and ops.blur_blend_u8 of the
+    copy over the working image, in place, inside mask_window(mask).  Returns uint8 [3, H, W] on the device (a channels-last view):
+    the bytes of the PIL image spot_fix returns."""
+    from . import ops
+    if image.dim() != 3:
+        raise ValueError(f"spot_fix_device: [3, H, W] image expected, got {tuple(image.shape)}")
+    mask = np.ascontiguousarray(np.asarray(mask_gray_u8))
+    if image.dtype != torch.uint8:
+        image = (255.0 * image.detach().float().clamp(0, 1)).to(torch.uint8)
+    work = image.detach().permute(1, 2, 0).contiguous()  # [H, W, 3]
+    if work.data_ptr() == image.data_ptr():
+        work = work.clone()
+    work_nchw = work.permute(2, 0, 1)[None]
+    mask_dev = torch.from_numpy(mask).to(work.device)
+    window = mask_window(mask)
+    size = (work.shape[1], work.shape[0])
+    for box in (mask_boxes(mask) if boxes is None else boxes):
+        plan = face_crop_plan(box, size, target_edge_len)
+        out = img2img_fn(crop_and_pad_device(work_nchw, plan))
+        if out.shape[-2:] != (plan.edge, plan.edge):
+            raise ValueError(f"img2img returned {tuple(out.shape)} for a {plan.edge}x{plan.edge} input")
+        pasted = work.clone()
+        unpad_resize_paste_device(pasted.permute(2, 0, 1)[None], out[:1].float(), plan, "paste")
+        ops.blur_blend_u8(work, pasted, mask_dev, out=work, window=window)
+    return work.permute(2, 0, 1)
+
+
+def spot_inpaint_device(image: torch.Tensor, mask_gray_u8: np.ndarray, inpaint_fn: Callable, max_edge_len: int = 768) -> torch.Tensor:
+    """`spot_inpaint` with the image staying on the device.  image: uint8 [H, W, 3] on the device; mask: the HOST uint8 [H, W] array,
+    uploaded once.  `inpaint_fn(crop, mask_crop, edge_len=max_edge_len)` gets views of the device image and mask and returns the
+    device uint8 [h, w, 3] patch (pipeline.inpaint_image with glue="device"), which is copied to the window's origin, clipped at the
+    image's border as PIL's paste clips it (spot_inpaint's QUIRK).  Returns a new uint8 [H, W, 3] tensor."""
+    if image.dim() != 3 or image.dtype != torch.uint8 or image.shape[2] != 3:
+        raise ValueError(f"spot_inpaint_device: uint8 [H, W, 3] image expected, got {image.dtype} {tuple(image.shape)}")
+    mask = np.ascontiguousarray(np.asarray(mask_gray_u8))
+    work = image.detach().clone()
+    box = mask_single_box(mask)
+    if box is None:
+        return work
+    H, W = work.shape[:2]
+    x, y, w, h = spot_window(box, (W, H), max_edge_len)
+    mask_dev = torch.from_numpy(mask).to(work.device)
+    patch = inpaint_fn(work[y:y + h, x:x + w], mask_dev[y:y + h, x:x + w], edge_len=max_edge_len)
+    ph, pw = min(int(patch.shape[0]), H - y), min(int(patch.shape[1]), W - x)
+    work[y:y + ph, x:x + pw] = patch[:ph, :pw, :3]  # not resized to the window: see spot_inpaint's QUIRK
+    return work
 
 
 # ---------------------------------------------------------------------------------------------- PNG + generation_data

@@ -554,6 +554,39 @@ typedef struct {
 } crg_poisson_args;
 int crg_poisson_clone(crg_ctx* ctx, void* stream, const crg_poisson_args* args);
 
+/* The blurred-mask composite of inpainting and spot inpainting (inpaint.py:373-392, spot_inpainter.py:1021-1039), on the device, one
+ * launch: cremage_amd.postprocess.blend_blurred_mask is the definition, and the bytes are equal.  Per image:
+ *   g[y][x]  = the mask's grey level: byte 0 of the mask pixel (gray_mode 0), or cv2's 14-bit fixed-point RGB -> GRAY of bytes 0..2,
+ *              (r * 4899 + g * 9617 + b * 1868 + 8192) >> 14 (gray_mode 1)
+ *   h[y][x]  = sum_i taps[i] * g[y][refl(x + i - 5)], v[y][x] = sum_i taps[i] * h[refl(y + i - 5)][x]   in float64: every product rounded,
+ *              the sum accumulated from i = 0 upwards, NO fused multiply-add; refl = BORDER_REFLECT_101 (-1 -> 1, n -> n - 2)
+ *   b        = clip(floor(v + 0.5), 0, 255)                                   cv.GaussianBlur(g, (11, 11), 0) as gaussian_blur_11 restates it
+ *   m = (float)b / 255.0f, t = 1.0f - m                                        fp32, the division correctly rounded
+ *   out[c]   = (uint8) trunc(clip(updated[c] * m + original[c] * t, 0, 255))  fp32, one rounding per operation, channels c < C
+ * taps: the eleven normalised Gaussian taps (sigma 2) as the HOST computes them - the device calls no exp.
+ * original, updated and out are strided uint8 images [N][H][W][C], C in 1..4, channels adjacent (pixel stride 3 or 4 bytes for RGB
+ * in an RGB or RGBA buffer); mask [N][H][W][1, 3 or 4].  Strides in bytes; mask_sn may be 0 (one mask for every image).  out may BE
+ * original (same pointer and strides: in place); otherwise out must not overlap original, and never updated or the mask.
+ * Window (win_w > 0): the caller states that every grey level outside the rectangle (win_x, win_y, win_w, win_h) INSET by 5 is 0, i.e.
+ * the rectangle is the bounding box of the non-zero grey levels grown by 5 (clamped to the image).  Tiles that do not touch it skip the
+ * blur: there m = 0 and the result is the original byte, exactly, so the bytes equal the run without a window.  win_w == 0: no window.
+ * H >= 6 and W >= 6 (what a radius-5 reflect-101 accepts).  No atomics, no host synchronisation, no allocation, no scratch. */
+typedef struct {
+  const void* original;    /* [N][H][W][C] uint8 */
+  int64_t org_sn, org_sy, org_sx;
+  const void* updated;     /* [N][H][W][C] uint8 */
+  int64_t upd_sn, upd_sy, upd_sx;
+  const void* mask;        /* [N][H][W][1 | 3 | 4] uint8 */
+  int64_t msk_sn, msk_sy, msk_sx;
+  int gray_mode;           /* 0: byte 0 as is, 1: cv2 RGB -> GRAY of bytes 0..2 */
+  void* out;               /* [N][H][W][C] uint8; may be `original` */
+  int64_t out_sn, out_sy, out_sx;
+  int N, H, W, C;
+  int win_x, win_y, win_w, win_h; /* win_w == 0: the whole image */
+  double taps[11];
+} crg_blend_args;
+int crg_blur_blend_u8(crg_ctx* ctx, void* stream, const crg_blend_args* args);
+
 /* y = a*x + b*y elementwise (IP-Adapter FaceID: out + ipa_scale * out_ipa, attention.py:681;
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
