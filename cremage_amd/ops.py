@@ -76,6 +76,18 @@ def _p(t: Optional[torch.Tensor]):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _is_dense(t: torch.Tensor) -> bool:
+    """Non-overlapping and dense: the tensor's elements are exactly the numel() consecutive ones behind data_ptr(), in some order of the
+    dims (contiguous, channels-last, ...).  What an elementwise kernel that walks numel() elements from the raw pointer needs; a slice
+    (gaps) or an expanded dim (stride 0) is not."""
+    want = 1
+    for size, stride in sorted(((sz, st) for sz, st in zip(t.shape, t.stride()) if sz != 1), key=lambda p: p[1]):
+        if stride != want:
+            return False
+        want *= size
+    return True
+
+
 # ---------------------------------------------------------------------------------- weight cache
 class TensorKeyedCache:
     """Cache of values derived from torch tensors (packed weights, fp32 copies, merged LoRA weights).
@@ -487,8 +499,13 @@ def nhwc_to_nchw(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 def affine_cast(x: torch.Tensor, a: float, b: float, dtype: torch.dtype, lo: float = float("-inf"), hi: float = float("inf")):
-    """y = clamp(a*x + b, lo, hi) cast to `dtype`, preserving strides (dense tensors only)."""
+    """y = clamp(a*x + b, lo, hi) cast to `dtype`.  A dense x (contiguous, channels-last, any permutation) keeps its strides; a view
+    with gaps or expanded dims is read through a compact copy in the same order of dims."""
     _need_cuda(x)
+    if not _is_dense(x):
+        x = x.clone(memory_format=torch.preserve_format)
+        if not _is_dense(x):
+            x = x.contiguous()
     y = torch.empty_strided(x.shape, x.stride(), dtype=dtype, device=x.device)
     h = _h(x)
     L.check(L.load().crg_affine_cast(h, _st(), _p(x), _p(y), x.numel(), a, b, lo, hi, _act_dt(x), _DT[dtype]), h, "crg_affine_cast")
@@ -558,9 +575,14 @@ def layer_norm(x: torch.Tensor, weight, bias, eps: float = 1e-5):
 
 
 def softmax_rows_(x: torch.Tensor, cols: int, scale: float):
-    """In-place softmax(x[:, :cols] * scale) over the last dim of a 2-D view with row stride x.shape[-1]."""
+    """In-place softmax(x[..., :cols] * scale) over the last dim of contiguous rows of stride x.shape[-1].  It writes through the raw
+    pointer, so it cannot repair a layout by copying: a view that is not contiguous rows raises."""
     _need_cuda(x)
+    if x.dim() < 1 or not x.is_contiguous():
+        raise L.CrgError(f"softmax_rows_: contiguous rows expected, got shape {tuple(x.shape)} with strides {x.stride()}")
     ld = x.shape[-1]
+    if not 0 < cols <= ld:
+        raise L.CrgError(f"softmax_rows_: {cols} columns in rows of {ld}")
     rows = x.numel() // ld
     h = _h(x)
     L.check(L.load().crg_softmax_rows(h, _st(), _p(x), _p(x), rows, cols, ld, scale, _act_dt(x)), h, "crg_softmax_rows")
@@ -861,6 +883,8 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     if cvec is not None:
         if cvec.dtype != torch.float32 or tuple(cvec.shape) != (n, cout) or cvec.stride(1) != 1 or cvec.stride(0) % 4:
             raise L.CrgError("conv2d: cvec must be fp32 [N, Cout] with unit column stride and 16-byte aligned rows")
+        if n > 1 and cvec.stride(0) < cout:  # one row expanded over the batch (stride 0): the C ABI reads a row stride of 0 as "Cout"
+            cvec = cvec.contiguous()
     a = L.ConvArgs(x=x.data_ptr(), x2=x2.data_ptr() if x2 is not None else None, C1=c1, C2=c2, w=hi.data_ptr(),
                    w_lo=lo.data_ptr() if lo is not None else None, bias=_p(f32_vec(bias)).value, cvec=_p(cvec).value,
                    cvec_ld=cvec.stride(0) if cvec is not None else 0, residual=_p(residual).value, y=y.data_ptr(), N=n, H=hh, W=ww, Cout=cout, Ho=ho, Wo=wo, ksize=ks, stride=stride,
@@ -974,11 +998,25 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
     non-finite ones (NaN, inf) would poison every output.  Every producer in this module (`linear_transposed`, `linear` /
     `ln_linear` with transposed_from) zeroes them; a caller that builds vt itself must do the same."""
     _need_cuda(q, k, vt)
+    if q.dim() != 3 or k.dim() != 3 or vt.dim() != 3:
+        raise L.CrgError("attention: q [B, Nq, C], k [B, Nk, C] and vt [B, C, ld] expected")
     B, Nq, Cc = q.shape
+    if heads <= 0 or Cc % heads:
+        raise L.CrgError(f"attention: width {Cc} does not split into {heads} heads")
+    if k.shape[0] != B or k.shape[2] != Cc or vt.shape[0] != B or vt.shape[1] != Cc:
+        raise L.CrgError(f"attention: k {tuple(k.shape)} / vt {tuple(vt.shape)} do not match q {tuple(q.shape)} in batch and width")
+    if k.dtype != q.dtype or vt.dtype != q.dtype:
+        raise L.CrgError(f"attention: q, k and vt must share one dtype, got {q.dtype}, {k.dtype}, {vt.dtype}")
+    if not 0 < n_keys <= min(k.shape[1], vt.shape[-1]):
+        raise L.CrgError(f"attention: n_keys = {n_keys} outside k's {k.shape[1]} rows / vt's {vt.shape[-1]} columns")
     Dh = Cc // heads
+    flash = q.dtype == HALF and Dh <= 160
+    if not flash and vt.shape[-1] < (n_keys + 7) // 8 * 8:
+        raise L.CrgError(f"attention: the unfused branch reads roundup(n_keys, 8) columns of vt, which has {vt.shape[-1]} for {n_keys} keys")
+    vt = vt.contiguous()  # no-op for the [B, C, ld] every producer of this module returns; ld is taken as the row stride below
     ld = vt.shape[-1]
     h = _h(q)
-    if q.dtype == HALF and Dh <= 160:
+    if flash:
         # q / k may be column slices of one fused projection output: rows keep their parent stride
         def rows(t):
             if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1):
@@ -1079,10 +1117,12 @@ def silu(x: torch.Tensor) -> torch.Tensor:
 
 
 def axpby_(y: torch.Tensor, x: torch.Tensor, a: float, b: float = 1.0) -> torch.Tensor:
-    """In place y = a*x + b*y (same dense layout on both sides)."""
+    """In place y = a*x + b*y (the same dense layout on both sides: the kernel walks numel() consecutive elements of each)."""
     _need_cuda(x, y)
     if x.shape != y.shape or x.stride() != y.stride() or x.dtype != y.dtype:
         raise L.CrgError("axpby_: operands must agree in shape, strides and dtype")
+    if not _is_dense(y):  # equal strides: x is then not dense either
+        raise L.CrgError(f"axpby_: operands must be dense (no gaps, no expanded dims), got shape {tuple(y.shape)} with strides {y.stride()}")
     h = _h(x)
     L.check(L.load().crg_axpby(h, _st(), _p(x), _p(y), x.numel(), a, b, _act_dt(x)), h, "crg_axpby")
     return _written(y)
