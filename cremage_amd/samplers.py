@@ -9,6 +9,9 @@ Mirrors (behaviour, names and argument meaning):
   sample_euler / sample_euler_ancestral / get_ancestral_step      modules/k_diffusion/sampling.py:51-58,118-163
   KDiffusionSamplerBase / EulerSampler / EulerAncestralSampler    modules/ldm/models/diffusion/k_diffusion_samplers.py:63-319
   DDIMSampler.make_schedule / stochastic_encode / decode          modules/ldm/models/diffusion/ddim.py:38-75,615-676
+
+The nine table-driven samplers (KSampler) are PLANS run by cremage_amd.sampler_plan's executors, which the SDXL samplers share; this
+file adds the plans only k_diffusion has and the CompVis wrapper's evaluator for the fused executor (_CompVisEvals).
 """
 from __future__ import annotations
 
@@ -18,15 +21,12 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import ops
+from .sampler_plan import (EDMDiscretization, _entry, _sigma_fn, _t_fn, append_zero, doubled_input, plan_dpmpp_2m,  # noqa: F401
+                           plan_dpmpp_2s_a, plan_draws, plan_heun, plan_lms, run_plan, with_time_rows)
+
 # dev knob: 0 = the fused sampler steps compute the CompVis wrapper's scalings and timestep per step (round 2) instead of once per run
 STEP_TABLES = __import__("os").environ.get("CRG_SAMPLER_TABLES", "1") != "0"
-
-
-def append_zero(x):
-    """x followed by one 0 (the terminal sigma of every k-diffusion schedule)."""
-    out = x.new_zeros(x.shape[0] + 1)
-    out[:-1] = x
-    return out
 
 
 def append_dims(x, target_dims):
@@ -178,20 +178,19 @@ class LDMWrapperForKDiffusion(nn.Module):
         _, c_in = cv.get_scalings(sigmas)
         return c_in, cv.sigma_to_t(sigmas)
 
-    def time_rows(self, t_rep):
-        """The wrapped UNet's timestep-only work for the whole table of timesteps `t_rep` [S, N] (`UNetModel.time_rows`) as (unet, rows),
-        or None when the network does not offer it; step i attaches rows[i] to its timesteps (`ops.attach_time_rows`)."""
-        dm = getattr(getattr(self.compviz_model.inner_model, "model", None), "diffusion_model", None)
-        f = getattr(dm, "time_rows", None)
-        from . import ops
-        return (dm, f(t_rep)) if (f is not None and t_rep.is_cuda and ops.TIME_ROWS) else None
+    def step_tables(self, sigmas, b):
+        """eps_tables of a run's evaluation sigmas as (c_in [S], the doubled batch's timestep rows): the rows carry the wrapped UNet's
+        timestep-only work for the whole table when it offers that (with_time_rows)."""
+        c_in, t_all = self.eps_tables(sigmas)
+        return c_in, with_time_rows(_unet_of(self.compviz_model.inner_model), t_all.reshape(-1, 1).expand(-1, 2 * b).contiguous())
 
     def eps_pair_pre(self, x, c_in_i, t_row):
-        """eps_pair with the step's scalars taken from eps_tables: `c_in_i` a 0-dim device tensor, `t_row` the step's timestep
+        """eps_pair with the step's scalars taken from step_tables: `c_in_i` a 0-dim device tensor, `t_row` the step's timestep
         already expanded to the doubled batch.  ONE elementwise launch builds cat([x] * 2) * c_in."""
-        xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-        torch.mul(x.unsqueeze(0).expand_as(xx), c_in_i, out=xx)
-        return self.compviz_model.get_eps(_mark_dup(xx.view((2 * x.shape[0],) + tuple(x.shape[1:]))), t_row, cond=self._cat_cond())
+        return self.compviz_model.get_eps(_mark_dup(doubled_input(x, c_in_i)), t_row, cond=self._cat_cond())
+
+    def fused_evals(self, ev, x):
+        return _CompVisEvals(self, ev, x)
 
     def fused_step_ok(self, x) -> bool:
         return (self.unconditional_conditioning is not None and self.unconditional_guidance_scale != 1. and x.is_cuda
@@ -234,9 +233,27 @@ def _mark_dup(x_in):
     said to the HIP UNet through a tensor attribute, which survives `apply_model` / `DiffusionWrapper.forward` of the reference's
     container as well (they pass x on untouched, ddpm.py:1034, :1517-1519)."""
     if x_in.is_cuda:
-        from . import ops
         ops.mark_cfg_dup(x_in)
     return x_in
+
+
+def _unet_of(ldm):
+    """The UNet of a LatentDiffusion-like container (ldm.model.diffusion_model), or None."""
+    return getattr(getattr(ldm, "model", None), "diffusion_model", None)
+
+
+class _CompVisEvals:
+    """The fused plan executor's evaluator (sampler_plan) over LDMWrapperForKDiffusion, under the conditions of its fused_step_ok:
+    every evaluation sigma of the run goes through eps_tables once and the UNet's timestep work is hoisted over the whole table; per
+    evaluation one eps_pair_pre input build (with the CFG mark) and the UNet.  c_out is the exact -sigma (CompVisDenoiser does not
+    snap it)."""
+
+    def __init__(self, model, ev, x):
+        self.model, self.cfg, self.c_out = model, model.unconditional_guidance_scale, [-v for v in ev.tolist()]
+        self.c_in, self.t_rows = model.step_tables(ev, x.shape[0])
+
+    def __call__(self, k, xin):
+        return self.model.eps_pair_pre(xin, self.c_in[k], self.t_rows[k]).contiguous(), self.c_out[k]
 
 
 def to_d(x, sigma, denoised):
@@ -264,18 +281,6 @@ def _host_sigmas(sigmas, sigmas_host):
     return sigmas.detach().float().cpu() if sigmas_host is None else sigmas_host
 
 
-def _with_time_rows(model, t_rep):
-    """The per-step rows of the timestep table [S, N] as a list, each carrying the UNet's hoisted timestep work when the wrapper
-    offers it (LDMWrapperForKDiffusion.time_rows)."""
-    rows = [t_rep[i] for i in range(t_rep.shape[0])]
-    tr = model.time_rows(t_rep) if hasattr(model, "time_rows") else None
-    if tr is not None:
-        from . import ops
-        for i, r in enumerate(rows):
-            ops.attach_time_rows(r, tr[1][i], tr[0])
-    return rows
-
-
 @torch.no_grad()
 def sample_euler(model, x, sigmas, extra_args=None, callback=None, disable=None, s_churn=0., s_tmin=0., s_tmax=float('inf'),
                  s_noise=1., sigmas_host=None):
@@ -289,9 +294,7 @@ def sample_euler(model, x, sigmas, extra_args=None, callback=None, disable=None,
     if fused:
         x = x.clone().contiguous()  # updated in place by the fused step
         if STEP_TABLES and s_churn == 0. and len(sigmas) > 1:  # sigma_hat == sigma on every step: the wrapper's per-step scalars from one vectorised pass
-            c_in_all, t_all = model.eps_tables(sigmas[:-1])
-            t_rep = t_all.reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous()
-            tables = (c_in_all, _with_time_rows(model, t_rep))
+            tables = model.step_tables(sigmas[:-1], x.shape[0])
     for i in range(len(sigmas) - 1):
         gamma = min(s_churn / (len(sigmas) - 1), 2 ** 0.5 - 1) if s_tmin <= sh[i].item() <= s_tmax else 0.
         eps = torch.randn_like(x) * s_noise
@@ -299,7 +302,6 @@ def sample_euler(model, x, sigmas, extra_args=None, callback=None, disable=None,
         if gamma > 0:
             x = x + eps * ((sigma_hat ** 2 - sh[i] ** 2) ** 0.5).item()
         if fused:  # scalings + guidance + Euler update as one kernel (include/crg_hip.h: crg_cfg_euler_step)
-            from . import ops
             e2 = model.eps_pair_pre(x, tables[0][i], tables[1][i]) if tables is not None else model.eps_pair(x, (sigmas[i] * (gamma + 1)) * s_in)
             ops.cfg_euler_step_(x, e2.contiguous(), None, sigma_hat.item(), (sh[i + 1] - sigma_hat).item(), model.unconditional_guidance_scale)
             continue
@@ -325,11 +327,9 @@ def sample_euler_ancestral(model, x, sigmas, extra_args=None, callback=None, dis
         x = x.clone().contiguous()  # updated in place by the fused step
         tables = STEP_TABLES and len(sigmas) > 1
         if tables:
-            c_in_all, t_all = model.eps_tables(sigmas[:-1])
-            t_rep = _with_time_rows(model, t_all.reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous())
+            c_in_all, t_rep = model.step_tables(sigmas[:-1], x.shape[0])
     for i in range(len(sigmas) - 1):
         if fused:  # scalings + guidance + Euler update + ancestral noise as one kernel (crg_cfg_euler_step)
-            from . import ops
             e2 = model.eps_pair_pre(x, c_in_all[i], t_rep[i]) if tables else model.eps_pair(x, sigmas[i] * s_in)
             sigma_down, sigma_up = get_ancestral_step(sh[i], sh[i + 1], eta=eta)
             noise = noise_sampler(sigmas[i], sigmas[i + 1]).contiguous() if sh[i + 1].item() > 0 else None
@@ -454,42 +454,13 @@ class EulerAncestralSampler(KDiffusionSamplerBase):
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # The rest of Cremage's SD1.5 sampler menu (cremage/utils/sampler_utils.py:21-34): Heun, DPM2, DPM2 A, LMS, DPM++ 2S A, DPM++ SDE,
-# DPM++ 2M, DPM++ 2M SDE, DPM++ 3M SDE (k_diffusion sampling.py:166-285, :516-710 behind k_diffusion_samplers.py:321-411).  A run is a
-# PLAN: the list of its UNet evaluations, built on the CPU from the host fp32 schedule, each with its sigma, the kind of update that
-# follows it, that update's scalars (Python floats holding the fp32 values of the reference's own torch expressions on 0-dim CPU
-# tensors, op for op) and the noise draw it makes.  Two executors run a plan through one loop (run_plan): torch arithmetic with one
-# fp32 rounding per reference operation, or one fused HIP launch per evaluation.
+# DPM++ 2M, DPM++ 2M SDE, DPM++ 3M SDE (k_diffusion sampling.py:166-285, :516-710 behind k_diffusion_samplers.py:321-411), each a PLAN
+# for sampler_plan.run_plan.  Heun, LMS, DPM++ 2S A and DPM++ 2M are sampler_plan's own plans; the others follow.
 
 def get_sigmas_karras(n, sigma_min=0.0316386, sigma_max=14.5521805, rho=7., device='cpu'):
     """The Karras et al. schedule followed by 0 (k_diffusion sampling.py:17-23), computed on the CPU in fp32 whatever `device`, so the
-    sigmas equal those of a CPU run of the reference bit for bit; the expression is sgm_hip.sampling.EDMDiscretization's."""
-    from .sgm_hip.sampling import EDMDiscretization
+    sigmas equal those of a CPU run of the reference bit for bit; the expression is EDMDiscretization's."""
     return EDMDiscretization(sigma_min, sigma_max, rho)(n, do_append_zero=True, device=device)
-
-
-def _t_fn(sigma):
-    return sigma.log().neg()
-
-
-def _sigma_fn(t):
-    return t.neg().exp()
-
-
-def _entry(sigma, kind, draw=None, **scalars):
-    """One UNet evaluation of a plan: its sigma, the update kind that consumes it, (sigma, sigma_next) of the noise draw made with it
-    (None: no draw) and the kind's scalars."""
-    return dict(sigma=float(sigma), kind=kind, draw=None if draw is None else (float(draw[0]), float(draw[1])), **scalars)
-
-
-def plan_heun(sh, eta=1., s_noise=1.):
-    """sample_heun with churn 0 (sampling.py:166-192): sigma_hat == sigma.  `tick`: the step's unused torch.randn_like draw (:173)."""
-    from .sgm_hip.sampling import edm_table
-    plan = []
-    for r in edm_table(sh, 1):
-        plan.append(_entry(r["sigma_hat"], "heun_1", dt=r["dt"], one_call=not r["two_call"], tick=True))
-        if r["two_call"]:
-            plan.append(_entry(r["next"], "heun_2", dt=r["dt"]))
-    return plan
 
 
 def _plan_dpm2(sh, ancestral, eta, s_noise):
@@ -516,27 +487,6 @@ def plan_dpm2_a(sh, eta=1., s_noise=1.):
     return _plan_dpm2(sh, True, eta, s_noise)
 
 
-def plan_lms(sh, eta=1., s_noise=1., order=4):
-    """sample_lms (sampling.py:268-285), order 4; the coefficients are sgm_hip.sampling.lms_table's (no scipy)."""
-    from .sgm_hip.sampling import lms_table
-    return [_entry(sh[i], "lms", coef=list(coef)) for i, coef in enumerate(lms_table(sh, order))]
-
-
-def plan_dpmpp_2s_a(sh, eta=1., s_noise=1.):
-    """sample_dpmpp_2s_ancestral (sampling.py:516-547); the scalars are sgm_hip.sampling.ancestral_table's (the same expressions)."""
-    from .sgm_hip.sampling import ancestral_table
-    plan = []
-    for r in ancestral_table(sh, 1, eta):
-        draw = (r["sigma"], r["next"]) if r["next"] > 0 else None
-        noisy = dict(draw=draw, sigma_up=r["sigma_up"], s_noise=s_noise)
-        if not r["two_call"]:
-            plan.append(_entry(r["sigma"], "dpmpp2s_1", dt=r["dt"], one_call=True, **noisy))
-            continue
-        plan.append(_entry(r["sigma"], "dpmpp2s_1", m=r["m"], one_call=False))
-        plan.append(_entry(r["s_sigma"], "dpmpp2s_2", m=r["m"], **noisy))
-    return plan
-
-
 def plan_dpmpp_sde(sh, eta=1., s_noise=1., r=0.5):
     """sample_dpmpp_sde (sampling.py:550-589) with r = 1/2: fac = 1, so denoised_d is the second evaluation's value and step 2 is
     DPM++ 2S's second update with the SDE's multipliers.  Both draws of a step start at sigma_fn(t)."""
@@ -557,13 +507,6 @@ def plan_dpmpp_sde(sh, eta=1., s_noise=1., r=0.5):
         plan.append(_entry(_sigma_fn(s), "dpmpp2s_2", m=[0., 0., float(_sigma_fn(t_next_) / _sigma_fn(t)), float((t - t_next_).expm1())],
                            sigma_up=float(su), s_noise=s_noise, draw=(_sigma_fn(t), _sigma_fn(t_next))))
     return plan
-
-
-def plan_dpmpp_2m(sh, eta=1., s_noise=1.):
-    """sample_dpmpp_2m (sampling.py:592-615); the multipliers are sgm_hip.sampling.dpmpp2m_multipliers' (the same expressions)."""
-    from .sgm_hip.sampling import dpmpp2m_multipliers
-    return [_entry(sh[i], "dpmpp2m", m=[m1, m2, 0. if m3 is None else m3, 0. if m4 is None else m4], advanced=bool(adv))
-            for i, (m1, m2, m3, m4, adv) in enumerate(dpmpp2m_multipliers(sh))]
 
 
 def plan_dpmpp_2m_sde(sh, eta=1., s_noise=1.):
@@ -637,11 +580,6 @@ def build_plan(key: str, sigmas_host, eta=1., s_noise=1.):
     return K_SAMPLERS[key][0](sigmas_host.detach().to("cpu", torch.float32), eta=eta, s_noise=s_noise)
 
 
-def plan_draws(plan) -> int:
-    """How often a run of the plan calls its noise sampler."""
-    return sum(1 for e in plan if e["draw"] is not None)
-
-
 class BrownianPairNoise:
     """Default noise of DPM++ SDE, whose two draws of a step cover overlapping sigma intervals that start at the same sigma: the
     increments of ONE Brownian motion over [sigma_i, sigma_s] and [sigma_i, sigma_next], each divided by the root of its length, are
@@ -666,191 +604,6 @@ class BrownianPairNoise:
             z = rho2 ** 0.5 * self.prev[2] + (1.0 - rho2) ** 0.5 * z
         self.prev = (s0, s1, z)
         return z
-
-
-def _add_noise(x, z, e):
-    return x + z * e["s_noise"] * e["sigma_up"]
-
-
-def _div(a, v: float):
-    """a / v as the reference divides: by a 0-dim tensor on a's device, a correctly rounded division.  With a Python number (or a
-    0-dim CPU tensor) as the divisor PyTorch's device kernel multiplies by the reciprocal, which differs in the last bit."""
-    return a / torch.full((), v, dtype=a.dtype, device=a.device)
-
-
-class _TorchSteps:
-    """A plan's updates in torch arithmetic, one fp32 rounding per reference operation: any device, any denoiser `model(x, sigma)`."""
-
-    def __init__(self, model, x):
-        self.model, self.x = model, x
-        self.x2 = self.d = None
-        self.hist = []  # LMS: derivatives, the multistep samplers: denoised values; newest first
-
-    def step(self, k, e, z):
-        xin = self.x2 if e["kind"] in ("heun_2", "dpm2_2", "dpmpp2s_2") else self.x
-        den = self.model(xin, torch.full((xin.shape[0],), e["sigma"], dtype=torch.float32, device=xin.device))
-        getattr(self, "_" + e["kind"])(e, den, z)
-
-    def _heun_1(self, e, den, z):
-        d = _div(self.x - den, e["sigma"])
-        x2 = self.x + d * e["dt"]
-        if e["one_call"]:
-            self.x = x2
-        else:
-            self.x2, self.d = x2, d
-
-    def _heun_2(self, e, den, z):
-        d2 = _div(self.x2 - den, e["sigma"])
-        self.x = self.x + ((self.d + d2) / 2) * e["dt"]
-
-    def _dpm2_2(self, e, den, z):
-        d2 = _div(self.x2 - den, e["sigma"])
-        self.x = self.x + d2 * e["dt"]
-        if z is not None:
-            self.x = _add_noise(self.x, z, e)
-
-    def _lms(self, e, den, z):
-        self.hist = [_div(self.x - den, e["sigma"])] + self.hist[:len(e["coef"]) - 1]
-        self.x = self.x + sum(c * d for c, d in zip(e["coef"], self.hist))
-
-    def _dpmpp2s_1(self, e, den, z):
-        if not e["one_call"]:
-            self.x2 = e["m"][0] * self.x - e["m"][1] * den
-            return
-        self.x = self.x + _div(self.x - den, e["sigma"]) * e["dt"]
-        if z is not None:
-            self.x = _add_noise(self.x, z, e)
-
-    def _dpmpp2s_2(self, e, den, z):
-        self.x = e["m"][2] * self.x - e["m"][3] * den
-        if z is not None:
-            self.x = _add_noise(self.x, z, e)
-
-    def _sde_1(self, e, den, z):
-        self.x2 = _add_noise(e["m"][0] * self.x - e["m"][1] * den, z, e)
-
-    def _dpmpp2m(self, e, den, z):
-        m1, m2, m3, m4 = e["m"]
-        self.x = m1 * self.x - m2 * ((m3 * den - m4 * self.hist[0]) if e["advanced"] else den)
-        self.hist = [den]
-
-    def _multistep(self, e, den, z, x):
-        if z is not None:
-            x = x + z * e["p"][0] * e["p"][1] * e["s_noise"]
-        self.x, self.hist = x, [den] + self.hist[:1]
-
-    def _sde_2m(self, e, den, z):
-        if e["last"]:
-            return self._multistep(e, den, None, den)
-        x = e["a"] * self.x + e["c1"] * den
-        if e["have_old"]:
-            x = x + e["c2"] * (den - self.hist[0])
-        self._multistep(e, den, z, x)
-
-    def _sde_3m(self, e, den, z):
-        if e["last"]:
-            return self._multistep(e, den, None, den)
-        x = e["a"] * self.x + e["c1"] * den
-        if e["order"] == 2:
-            x = x + e["phi2"] * _div(den - self.hist[0], e["r"][0])
-        elif e["order"] == 3:
-            r0, r1 = e["r"]
-            d1_0, d1_1 = _div(den - self.hist[0], r0), _div(self.hist[0] - self.hist[1], r1)
-            d1 = d1_0 + _div((d1_0 - d1_1) * r0, e["rsum"])
-            d2 = _div(d1_0 - d1_1, e["rsum"])
-            x = x + e["phi2"] * d1 - e["phi3"] * d2
-        self._multistep(e, den, z, x)
-
-
-class _FusedSteps:
-    """A plan's updates as one fused HIP launch per evaluation (crg_cfg_sampler_step, crg_cfg_dpmpp2m_step, crg_cfg_kstep), under
-    the conditions of LDMWrapperForKDiffusion.fused_step_ok.  Every evaluation sigma of the run goes through eps_tables once and the
-    UNet's timestep work is hoisted over the whole table; per evaluation one eps_pair_pre input build, the UNet and one step launch.
-    c_out is the exact -sigma (CompVisDenoiser does not snap it).  Works on a copy of x."""
-
-    def __init__(self, model, x, plan):
-        self.model, self.cfg = model, model.unconditional_guidance_scale
-        self.x = x.clone().contiguous()  # updated in place
-        c_in_all, t_all = model.eps_tables(torch.tensor([e["sigma"] for e in plan], dtype=torch.float32))
-        self.c_in = c_in_all
-        self.t_rows = _with_time_rows(model, t_all.reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous())
-        kinds = {e["kind"] for e in plan}
-        self.x2 = torch.empty_like(self.x) if kinds & {"heun_2", "dpm2_2", "dpmpp2s_2"} else None
-        self.d = torch.empty_like(self.x) if kinds & {"heun_2", "dpm2_2"} else None
-        n_ring = 4 if "lms" in kinds else 3 if "sde_3m" in kinds else 2 if "sde_2m" in kinds else 1 if "dpmpp2m" in kinds else 0
-        self.ring, self.n = [torch.empty_like(self.x) for _ in range(n_ring)], 0  # n: multistep evaluations so far
-
-    def step(self, k, e, z):
-        from . import ops
-        second = e["kind"] in ("heun_2", "dpm2_2", "dpmpp2s_2")
-        eps2 = self.model.eps_pair_pre(self.x2 if second else self.x, self.c_in[k], self.t_rows[k]).contiguous()
-        noisy = {} if z is None else dict(noise=z.contiguous(), s_noise=e["s_noise"], add_noise=True)
-        getattr(self, "_" + e["kind"])(ops, e, (self.x, eps2, -e["sigma"], self.cfg), noisy)
-
-    def _heun_1(self, ops, e, head, noisy):
-        ops.cfg_sampler_step_("heun_1", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, d=self.d, one_call=e["one_call"])
-
-    def _heun_2(self, ops, e, head, noisy):
-        ops.cfg_sampler_step_("heun_2", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, d=self.d)
-
-    def _dpmpp2s_1(self, ops, e, head, noisy):
-        if e["one_call"]:
-            ops.cfg_sampler_step_("dpmpp2s_1", *head, sigma=e["sigma"], dt=e["dt"], one_call=True, sigma_up=e["sigma_up"], **noisy)
-        else:
-            ops.cfg_sampler_step_("dpmpp2s_1", *head, x2=self.x2, m=e["m"])
-
-    def _dpmpp2s_2(self, ops, e, head, noisy):
-        ops.cfg_sampler_step_("dpmpp2s_2", *head, x2=self.x2, m=e["m"], sigma_up=e["sigma_up"], **noisy)
-
-    def _lms(self, ops, e, head, noisy):
-        n, self.n = self.n, self.n + 1
-        hist = [self.ring[(n - j) % 4] for j in range(1, len(e["coef"]))]
-        ops.cfg_sampler_step_("lms", *head, sigma=e["sigma"], d=self.ring[n % 4], hist=hist, coef=e["coef"])
-
-    def _dpmpp2m(self, ops, e, head, noisy):
-        ops.cfg_dpmpp2m_step_(head[0], head[1], self.ring[0], head[2], head[3], *e["m"], e["advanced"])
-
-    def _dpm2_2(self, ops, e, head, noisy):
-        ops.cfg_kstep_("dpm2_2", *head, sigma=e["sigma"], dt=e["dt"], x2=self.x2, sigma_up=e["sigma_up"], **noisy)
-
-    def _sde_1(self, ops, e, head, noisy):
-        ops.cfg_kstep_("sde_1", *head, x2=self.x2, m=e["m"], sigma_up=e["sigma_up"], **noisy)
-
-    def _multistep(self, ops, e, head, noisy, n_old, **scalars):
-        """This step's denoised value goes to the ring slot the step does not read; `n_old` previous ones are handed over, newest first."""
-        n, self.n, r = self.n, self.n + 1, len(self.ring)
-        ops.cfg_kstep_(e["kind"], *head, den_out=self.ring[n % r], old=[self.ring[(n - j) % r] for j in range(1, n_old + 1)],
-                       last=e["last"], **scalars, **noisy)
-
-    def _sde_2m(self, ops, e, head, noisy):
-        if e["last"]:
-            return self._multistep(ops, e, head, {}, 0)
-        self._multistep(ops, e, head, noisy, int(e["have_old"]), a=e["a"], c1=e["c1"], c2=e.get("c2", 0.), p=e.get("p", (0., 0.)),
-                        have_old=e["have_old"])
-
-    def _sde_3m(self, ops, e, head, noisy):
-        if e["last"]:
-            return self._multistep(ops, e, head, {}, 0)
-        self._multistep(ops, e, head, noisy, e["order"] - 1, a=e["a"], c1=e["c1"], p=e.get("p", (0., 0.)), r=e.get("r", (0., 0.)),
-                        rsum=e.get("rsum", 0.), phi2=e.get("phi2", 0.), phi3=e.get("phi3", 0.), order=e["order"])
-
-
-@torch.no_grad()
-def run_plan(model, x, plan, noise_sampler=None, fused=None):
-    """Run a plan from x (not mutated): per evaluation the noise draw it makes - `noise_sampler(sigma, sigma_next)` with 0-dim CPU fp32
-    tensors, in the order, number and with the arguments of the reference's own calls; torch.randn_like by default - then the
-    evaluation and its update.  `fused`: None = whenever model.fused_step_ok(x), False = the torch executor."""
-    if noise_sampler is None:
-        noise_sampler = default_noise_sampler(x)
-    if fused is None:
-        fused = getattr(model, "fused_step_ok", lambda _x: False)(x)
-    ex = _FusedSteps(model, x, plan) if fused else _TorchSteps(model, x)
-    for k, e in enumerate(plan):
-        if e.get("tick"):
-            torch.randn_like(x)  # keeps the global RNG stream where the reference leaves it (see sample_euler)
-        z = noise_sampler(torch.tensor(e["draw"][0]), torch.tensor(e["draw"][1])) if e["draw"] is not None else None
-        ex.step(k, e, z)
-    return ex.x
 
 
 class KSampler(KDiffusionSamplerBase):
@@ -980,18 +733,18 @@ class DDIMSampler(object):
         DDIMSampler._cat_memo = (leaves, tuple(t._version for _, _, t in leaves), c_in)
         return c_in
 
-    def _time_rows(self, t_rep):
-        """The HIP UNet's hoisted timestep work for the table of doubled timesteps `t_rep` [S, 2b] (UNetModel.time_rows), attached
-        to the per-step rows; plain rows when the network does not offer it."""
-        from . import ops
-        rows = [t_rep[i] for i in range(t_rep.shape[0])]
-        dm = getattr(getattr(self.model, "model", None), "diffusion_model", None)
-        f = getattr(dm, "time_rows", None)
-        if f is not None and t_rep.is_cuda and ops.TIME_ROWS:
-            tr = f(t_rep)
-            for i, r in enumerate(rows):
-                ops.attach_time_rows(r, tr[i], dm)
-        return rows
+    def _fused_loop(self, x, time_range, noise, scale):
+        """The fused executor of `sample` and `decode` over the descending timesteps `time_range` from x (not mutated), with the doubled
+        conditioning in self._c_in: the UNet's timestep work hoisted over the whole range (with_time_rows), then per step one doubled-
+        input copy, the UNet and crg_cfg_ddim_step with the step scalars of make_schedule.  `noise(index, x)`: the step's z, or None."""
+        x, b = x.clone().contiguous(), x.shape[0]  # updated in place by the fused step
+        t_rep = torch.tensor(time_range.copy(), dtype=torch.long).reshape(-1, 1).expand(-1, 2 * b).contiguous().to(x.device)
+        for i, t_row in enumerate(with_time_rows(_unet_of(self.model), t_rep)):
+            index = len(time_range) - i - 1
+            z = noise(index, x)
+            e2 = self.model.apply_model(_mark_dup(doubled_input(x)), t_row, self._c_in)
+            ops.cfg_ddim_step_(x, e2.contiguous(), z.contiguous() if z is not None else None, scale, *self._step_scalars[index])
+        return x
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, eta=0., x_T=None, verbose=False,
@@ -1014,27 +767,21 @@ class DDIMSampler(object):
         self._c_in = self._cat_cond(conditioning, uc) if guided else None
         time_range = np.flip(self.ddim_timesteps)
         total = self.ddim_timesteps.shape[0]
-        fused = guided and callback is None and x.is_cuda and x.dtype == torch.float32
-        if fused:
-            from . import ops
-            x = x.clone().contiguous()  # updated in place by the fused step
-            t_rep = torch.tensor(time_range.copy(), dtype=torch.long).reshape(-1, 1).expand(-1, 2 * batch_size).contiguous().to(x.device)
-            t_rows = self._time_rows(t_rep)
+
+        def noise(index, x):
+            sigma = self._step_scalars[index][4]
+            if sigma == 0.:
+                return None
+            return noise_sampler(sigma, index) if noise_sampler is not None else torch.randn(size, device=x.device)
+        if guided and callback is None and x.is_cuda and x.dtype == torch.float32:
+            x = self._fused_loop(x, time_range, noise, scale)
+            self._c_in = None
+            return x, None
         for i, step in enumerate(time_range):
             index = total - i - 1
-            sigma = self._step_scalars[index][4]
-            z = None
-            if sigma != 0.:
-                z = noise_sampler(sigma, index) if noise_sampler is not None else torch.randn(size, device=x.device)
-            if fused:
-                xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-                xx.copy_(x.unsqueeze(0).expand_as(xx))  # cat([x] * 2) as one copy
-                e2 = self.model.apply_model(_mark_dup(xx.view((2 * batch_size,) + tuple(x.shape[1:]))), t_rows[i], self._c_in)
-                ops.cfg_ddim_step_(x, e2.contiguous(), z.contiguous() if z is not None else None, scale, *self._step_scalars[index])
-                continue
             ts = torch.full((batch_size,), int(step), device=x.device, dtype=torch.long)
             x, _ = self.p_sample_ddim(x, conditioning, ts, index=index, unconditional_guidance_scale=scale,
-                                      unconditional_conditioning=uc, noise=z)
+                                      unconditional_conditioning=uc, noise=noise(index, x))
             if callback:
                 callback(i)
         self._c_in = None
@@ -1061,17 +808,9 @@ class DDIMSampler(object):
         if guided:
             self._c_in = self._cat_cond(cond, uc) if isinstance(cond, dict) else torch.cat([uc, cond])
         if guided and isinstance(cond, dict) and callback is None and x_latent.is_cuda and x_latent.dtype == torch.float32:
-            from . import ops
-            x, b = x_latent.clone().contiguous(), x_latent.shape[0]  # updated in place by the fused step
-            t_rep = torch.tensor(time_range.copy(), dtype=torch.long).reshape(-1, 1).expand(-1, 2 * b).contiguous().to(x.device)
-            t_rows = self._time_rows(t_rep)
-            for i in range(total_steps):
-                sc = self._step_scalars[total_steps - i - 1]
-                z = torch.randn_like(x) if sc[4] != 0. else None  # noise_like of a schedule made with eta > 0 (ddim.py:603)
-                xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-                xx.copy_(x.unsqueeze(0).expand_as(xx))  # cat([x] * 2) as one copy
-                e2 = self.model.apply_model(_mark_dup(xx.view((2 * b,) + tuple(x.shape[1:]))), t_rows[i], self._c_in)
-                ops.cfg_ddim_step_(x, e2.contiguous(), z, scale, *sc)
+            # noise_like of a schedule made with eta > 0 (ddim.py:603)
+            x = self._fused_loop(x_latent, time_range, lambda index, x: torch.randn_like(x) if self._step_scalars[index][4] != 0. else None,
+                                 scale)
             self._c_in = None
             return x
         x_dec = x_latent

@@ -2,17 +2,20 @@
 modules/sdxl/sgm/modules/diffusionmodules/{denoiser.py:10-75, denoiser_scaling.py:29-37, discretizer.py:17-78,
 guiders.py:24-65, sampling.py:29-573, sampling_utils.py:7-51, wrappers.py:24-34} and DiffusionEngine.decode_first_stage
 (sgm/models/diffusion.py:118-136).  Tensors here are [b, 4, L, L] latents and per-sample scalars; the per-step cost
-is the UNet call."""
+is the UNet call.  Every sampler but EulerEDM is a plan run by cremage_amd.sampler_plan's executors (what the SD1.5 k-diffusion
+samplers run through as well); the scalar tables the plans are built from live there and are re-exported here."""
 from __future__ import annotations
 
-import functools
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from ..samplers import append_dims, append_zero, make_beta_schedule
+from ..sampler_plan import (EDMDiscretization, ancestral_table, append_zero, doubled_input, dpmpp2m_multipliers, edm_table,  # noqa: F401
+                            get_ancestral_step, linear_multistep_coeff, lms_table, plan_dpmpp_2m, plan_dpmpp_2s_a, plan_euler_a, plan_heun,
+                            plan_lms, run_plan)
+from ..samplers import append_dims, make_beta_schedule
 
 
 class LegacyDDPMDiscretization:
@@ -33,29 +36,6 @@ class LegacyDDPMDiscretization:
             raise ValueError
         sigmas = torch.tensor((1 - alphas_cumprod) / alphas_cumprod, dtype=torch.float32, device=device) ** 0.5
         return torch.flip(sigmas, (0,))
-
-    def __call__(self, n, do_append_zero=True, device="cpu", flip=False):
-        sigmas = self.get_sigmas(n, device=device)
-        sigmas = append_zero(sigmas) if do_append_zero else sigmas
-        return sigmas if not flip else torch.flip(sigmas, (0,))
-
-
-class EDMDiscretization:
-    """discretizer.py:28-48 (+ Discretization.__call__ :17-24): the Karras et al. schedule.  Always computed on the CPU in fp32 with
-    the reference's torch expression, then moved to `device`, so a run's sigmas equal those of a CPU run of the reference bit for
-    bit whatever the device."""
-
-    def __init__(self, sigma_min=0.002, sigma_max=80.0, rho=7.0):
-        self.sigma_min = sigma_min
-        self.sigma_max = sigma_max
-        self.rho = rho
-
-    def get_sigmas(self, n, device="cpu"):
-        ramp = torch.linspace(0, 1, n)
-        min_inv_rho = self.sigma_min ** (1 / self.rho)
-        max_inv_rho = self.sigma_max ** (1 / self.rho)
-        sigmas = (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** self.rho
-        return sigmas.to(device)
 
     def __call__(self, n, do_append_zero=True, device="cpu", flip=False):
         sigmas = self.get_sigmas(n, device=device)
@@ -251,219 +231,38 @@ class EulerEDMSampler:
         return x
 
 
-def _to_neg_log_sigma(sigma):
-    return sigma.log().neg()  # sampling_utils.py:46-47
-
-
-def _to_sigma(neg_log_sigma):
-    return neg_log_sigma.neg().exp()  # sampling_utils.py:50-51
-
-
-def dpmpp2m_multipliers(sigmas: torch.Tensor):
-    """Per step i of a DPM++ 2M run over the CPU fp32 schedule `sigmas`: (m1, m2, m3, m4, advanced) as Python floats holding fp32
-    values.  The arithmetic is DPMPP2MSampler.get_variables / get_mult (sampling.py:460-486) op for op in fp32 torch on the CPU, so
-    the scalars equal those of a CPU run of the reference bit for bit.  m3 / m4 are None on the first step; `advanced` is False on the
-    first step and on a step whose next sigma is 0 (sampling.py:539-548)."""
-    sigmas = sigmas.detach().to("cpu", torch.float32)
-    out = []
-    for i in range(len(sigmas) - 1):
-        sigma, next_sigma = sigmas[i:i + 1], sigmas[i + 1:i + 2]
-        t, t_next = _to_neg_log_sigma(sigma), _to_neg_log_sigma(next_sigma)
-        h = t_next - t
-        m1 = _to_sigma(t_next) / _to_sigma(t)
-        m2 = (-h).expm1()
-        m3 = m4 = None
-        if i > 0:
-            r = (t - _to_neg_log_sigma(sigmas[i - 1:i])) / h
-            m3, m4 = float(1 + 1 / (2 * r)), float(1 / (2 * r))
-        out.append((float(m1), float(m2), m3, m4, i > 0 and float(next_sigma) > 0.0))
-    return out
-
-
-class DPMPP2MSampler:
-    """sampling.py:29-137,459-573: DPM++ 2M (multistep, second order) with CFG, Cremage's default SDXL sampler
-    (preferences.py:159).  The schedule is computed once on the CPU (and moved to the device), the multipliers once per run
-    (dpmpp2m_multipliers).  `x *= sqrt(1 + sigma_0^2)` is kept, on a copy: the caller's tensor is not mutated.
-
-    Fused path (CUDA fp32 latents, VanillaCFG with scale != 1, the engine's denoiser and network passed as `parts`): per step one
-    launch builds cat([x] * 2) * c_in, the network runs, and crg_cfg_dpmpp2m_step does the denoiser scalings, the guidance and the
-    update in one launch.  Otherwise the torch loop below, which runs on the CPU as well."""
-
-    def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", fused: bool = True):
-        self.num_steps = num_steps
-        self.discretization = LegacyDDPMDiscretization()
-        self.guider = guider
-        self.device = device
-        self.fused = fused
-
-    def denoise(self, x, denoiser, sigma, cond, uc):
-        denoised = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))
-        return self.guider(denoised, sigma)
-
-    def fused_ok(self, x, parts) -> bool:
-        return (self.fused and parts is not None and x.is_cuda and x.dtype == torch.float32 and isinstance(self.guider, VanillaCFG)
-                and self.guider.scale != 1.0)
-
-    @torch.no_grad()
-    def __call__(self, denoiser, x, cond, uc=None, num_steps=None, parts=None):
-        """`parts` = (DiscreteDenoiser, network): the pieces `denoiser` applies, for the fused path."""
-        n = self.num_steps if num_steps is None else num_steps
-        sh = self.discretization(n, device="cpu").float()
-        uc = cond if uc is None else uc
-        mults = dpmpp2m_multipliers(sh)
-        x = x * float(torch.sqrt(1.0 + sh[0] ** 2.0))
-        if self.fused_ok(x, parts):
-            return self._fused(parts[0], parts[1], x.contiguous(), cond, uc, sh, mults)
-        sigmas = sh.to(x.device)
-        s_in = x.new_ones([x.shape[0]])
-        old_denoised = None
-        for i, (m1, m2, m3, m4, advanced) in enumerate(mults):
-            denoised = self.denoise(x, denoiser, s_in * sigmas[i], cond, uc)
-            if advanced:
-                x = m1 * x - m2 * (m3 * denoised - m4 * old_denoised)
-            else:
-                x = m1 * x - m2 * denoised
-            old_denoised = denoised
-        return x
-
-    def _fused(self, dd: "DiscreteDenoiser", network, x, cond, uc, sh, mults):
-        from .. import ops
-        b = x.shape[0]
-        table = dd.sigmas.detach().cpu()
-        idx = (sh[:-1] - table[:, None]).abs().argmin(dim=0)  # DiscreteDenoiser.sigma_to_idx for every step at once
-        sq = table[idx]                                       # quantised sigmas: c_out = -sq
-        c_in = 1 / (sq.to(x.device) ** 2 + 1.0) ** 0.5        # EpsScaling, the same device arithmetic as the per-step path
-        t_rows = idx.to(x.device).reshape(-1, 1).expand(-1, 2 * b).contiguous()  # c_noise = sigma_to_idx(sigma_q)
-        cc = self.guider.cat_cond(cond, uc)
-        old = torch.empty_like(x)  # read from the second step on only
-        for i, (m1, m2, m3, m4, advanced) in enumerate(mults):
-            xx = torch.empty((2,) + tuple(x.shape), dtype=x.dtype, device=x.device)
-            torch.mul(x.unsqueeze(0).expand_as(xx), c_in[i], out=xx)
-            eps2 = network(xx.view((2 * b,) + tuple(x.shape[1:])), t_rows[i], cc)
-            ops.cfg_dpmpp2m_step_(x, eps2.contiguous(), old, -float(sq[i]), self.guider.scale, m1, m2,
-                                  0.0 if m3 is None else m3, 0.0 if m4 is None else m4, advanced)
-        return x
-
-
-def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
-    """sampling_utils.py:22-39 (on the CPU fp32 [b] vectors of the schedule)."""
-    if not eta:
-        return sigma_to, torch.zeros_like(sigma_to)  # the reference returns a Python 0.0 here, which its append_dims rejects
-    sigma_up = torch.minimum(sigma_to, eta * (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5)
-    sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
-    return sigma_down, sigma_up
-
-
-@functools.lru_cache(maxsize=None)
-def _gauss_legendre(n: int):
-    nodes, weights = np.polynomial.legendre.leggauss(n)
-    return tuple(float(v) for v in nodes), tuple(float(v) for v in weights)
-
-
-def linear_multistep_coeff(order: int, t, i: int, j: int) -> float:
-    """sampling_utils.py:7-19 without scipy: the integral of the Lagrange basis polynomial j (degree order - 1) over [t[i], t[i+1]] by
-    float64 Gauss-Legendre quadrature with `order` nodes, exact for that degree.  The reference's adaptive scipy.integrate.quad
-    evaluates its integrand in float32 (NumPy 2 keeps the float32 schedule's precision), so its coefficients and these differ in the
-    last fp32 bits (<= 3e-7 relative)."""
-    if order - 1 > i:
-        raise ValueError(f"Order {order} too high for step {i}")
-    nodes, weights = _gauss_legendre(max(order, 1))
-    a, b = float(t[i]), float(t[i + 1])
-    half, mid = 0.5 * (b - a), 0.5 * (b + a)
-    tj = float(t[i - j])
-    tk = [float(t[i - k]) for k in range(order) if k != j]
-    total = 0.0
-    for x, w in zip(nodes, weights):
-        tau = half * x + mid
-        prod = 1.0
-        for v in tk:
-            prod *= (tau - v) / (tj - v)
-        total += w * prod
-    return half * total
-
-
-def edm_table(sigmas: torch.Tensor, b: int, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf")):
-    """Per step of EDMSampler.__call__ / sampler_step (sampling.py:165-219, :332-358) over the CPU fp32 schedule, with the reference's
-    torch expressions on [b] vectors: dicts of Python floats holding fp32 values - sigma_hat, the churn noise's std (None when
-    gamma == 0: no draw), dt = next - sigma_hat, next, and two_call (HeunEDM's second evaluation, sum(next) >= 1e-14)."""
-    sigmas = sigmas.detach().to("cpu", torch.float32)
-    s_in, num = torch.ones([b]), len(sigmas)
-    rows = []
-    for i in range(num - 1):
-        sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
-        gamma = min(s_churn / (num - 1), 2 ** 0.5 - 1) if s_tmin <= sigmas[i] <= s_tmax else 0.0
-        sigma_hat = sigma * (gamma + 1.0)
-        churn = float(((sigma_hat ** 2 - sigma ** 2) ** 0.5)[0]) if gamma > 0 else None
-        rows.append(dict(sigma_hat=float(sigma_hat[0]), churn=churn, dt=float((nxt - sigma_hat)[0]), next=float(nxt[0]),
-                         two_call=not bool(torch.sum(nxt) < 1e-14)))
-    return rows
-
-
-def ancestral_table(sigmas: torch.Tensor, b: int, eta=1.0, multipliers: bool = True):
-    """Per step of AncestralSampler / DPMPP2SAncestralSampler (sampling.py:222-268, :384-456) over the CPU fp32 schedule, with the
-    reference's torch expressions on [b] vectors: sigma, next, sigma_down, sigma_up, dt = sigma_down - sigma, two_call (DPM++ 2S's
-    second evaluation, sum(sigma_down) >= 1e-14) and, on a two-call step with `multipliers`, DPM++ 2S's m1..m4 and its second
-    evaluation sigma to_sigma(s) (None otherwise)."""
-    sigmas = sigmas.detach().to("cpu", torch.float32)
-    s_in = torch.ones([b])
-    rows = []
-    for i in range(len(sigmas) - 1):
-        sigma, nxt = s_in * sigmas[i], s_in * sigmas[i + 1]
-        down, up = get_ancestral_step(sigma, nxt, eta=eta)
-        two_call = not bool(torch.sum(down) < 1e-14)
-        m, s_sigma = None, None
-        if two_call and multipliers:
-            t, t_next = _to_neg_log_sigma(sigma), _to_neg_log_sigma(down)   # get_variables
-            h = t_next - t
-            s = t + 0.5 * h
-            m = [float(v[0]) for v in (_to_sigma(s) / _to_sigma(t), (-0.5 * h).expm1(), _to_sigma(t_next) / _to_sigma(t), (-h).expm1())]
-            s_sigma = float(_to_sigma(s)[0])
-        rows.append(dict(sigma=float(sigma[0]), next=float(nxt[0]), sigma_down=float(down[0]), sigma_up=float(up[0]),
-                         dt=float((down - sigma)[0]), two_call=two_call, m=m, s_sigma=s_sigma))
-    return rows
-
-
-def lms_table(sigmas: torch.Tensor, order: int):
-    """Per step of LinearMultistepSampler.__call__ (sampling.py:282-306): the coefficients, newest derivative first."""
-    t = sigmas.detach().to("cpu", torch.float32).tolist()
-    out = []
-    for i in range(len(t) - 1):
-        cur = min(i + 1, order)
-        out.append([linear_multistep_coeff(cur, t, i, j) for j in range(cur)])
-    return out
-
-
 def snap_to_table(table: torch.Tensor, sigmas: torch.Tensor) -> torch.Tensor:
     """DiscreteDenoiser.sigma_to_idx (denoiser.py:54-56) of every sigma at once, on the CPU: the index of the nearest table entry."""
     return (sigmas - table[:, None]).abs().argmin(dim=0)
 
 
-class _FusedEvals:
-    """The fused path's denoiser inputs for a run's evaluation sigmas `ev` (CPU fp32, in call order): DiscreteDenoiser.sigma_to_idx
-    for all of them at once, the snapped sigmas (c_out = -sq), c_in with the per-call path's device arithmetic and the timestep rows."""
+class _DiscreteEvals:
+    """The fused plan executor's evaluator (sampler_plan) over the engine's DiscreteDenoiser `dd` and network, with the guider's doubled
+    conditioning `cc` and scale `cfg`.  fused_evals, once per run: DiscreteDenoiser.sigma_to_idx for all evaluation sigmas at once, the
+    snapped sigmas (c_out = -sq), c_in with the per-call path's device arithmetic and the timestep rows (the table indices; the SDXL
+    UNet hoists no timestep work).  Per evaluation one input build and the network."""
 
-    def __init__(self, dd: "DiscreteDenoiser", network, ev: torch.Tensor, x: torch.Tensor, cc: Dict):
-        table = dd.sigmas.detach().cpu()
-        idx = snap_to_table(table, ev)
-        self.sq = [float(v) for v in table[idx]]
-        self.c_in = 1 / (table[idx].to(x.device) ** 2 + 1.0) ** 0.5
+    def __init__(self, dd: "DiscreteDenoiser", network, cc: Dict, cfg: float):
+        self.table, self.network, self.cc, self.cfg = dd.sigmas.detach().cpu(), network, cc, cfg
+
+    def fused_evals(self, ev: torch.Tensor, x: torch.Tensor):
+        idx = snap_to_table(self.table, ev)
+        sq = self.table[idx]
+        self.c_out = [-v for v in sq.tolist()]
+        self.c_in = 1 / (sq.to(x.device) ** 2 + 1.0) ** 0.5
         self.t_rows = idx.to(x.device).reshape(-1, 1).expand(-1, 2 * x.shape[0]).contiguous()
-        self.network, self.cc, self.k = network, cc, 0
+        return self
 
-    def __call__(self, xin: torch.Tensor):
-        """The next evaluation: one input build, the network; returns (eps [2b, ...], c_out)."""
-        k, self.k = self.k, self.k + 1
-        xx = torch.empty((2,) + tuple(xin.shape), dtype=xin.dtype, device=xin.device)
-        torch.mul(xin.unsqueeze(0).expand_as(xx), self.c_in[k], out=xx)
-        eps2 = self.network(xx.view((2 * xin.shape[0],) + tuple(xin.shape[1:])), self.t_rows[k], self.cc)
-        return eps2.contiguous(), -self.sq[k]
+    def __call__(self, k: int, xin: torch.Tensor):
+        return self.network(doubled_input(xin, self.c_in[k]), self.t_rows[k], self.cc).contiguous(), self.c_out[k]
 
 
 class _KSampler:
-    """Shared plumbing of HeunEDM, EulerAncestral, DPM++ 2S ancestral and LMS: the schedule on the CPU (what steers the loop) and on
-    the device, prepare_sampling_loop's `x *= sqrt(1 + sigma_0^2)` on a copy, and the choice of path.  Fused path (CUDA fp32 latents,
-    VanillaCFG with scale != 1, the engine's denoiser and network as `parts`): per UNet evaluation one input build, the network and
-    one crg_cfg_sampler_step launch.  Otherwise the torch loop, which restates the reference and runs on the CPU as well."""
+    """The five samplers that run as plans (cremage_amd.sampler_plan): the schedule on the CPU (what steers the run),
+    prepare_sampling_loop's `x *= sqrt(1 + sigma_0^2)` on a copy (the caller's tensor is not mutated), the sampler's plan over that
+    schedule, and the choice of executor.  Fused (CUDA fp32 latents, VanillaCFG with scale != 1, the engine's denoiser and network as
+    `parts`): per UNet evaluation one input build, the network and one fused step launch, which does the denoiser scalings, the guidance
+    and the update.  Otherwise the torch executor around `denoise`, which restates the reference and runs on the CPU as well."""
 
     def __init__(self, num_steps: int, guider: VanillaCFG, device="cuda", fused: bool = True):
         self.num_steps = num_steps
@@ -480,6 +279,10 @@ class _KSampler:
         return (self.fused and parts is not None and x.is_cuda and x.dtype == torch.float32 and isinstance(self.guider, VanillaCFG)
                 and self.guider.scale != 1.0)
 
+    def plan(self, sh, b):
+        """The run's plan over the CPU fp32 schedule `sh` for a batch of b."""
+        raise NotImplementedError
+
     @torch.no_grad()
     def __call__(self, denoiser, x, cond, uc=None, num_steps=None, parts=None):
         """`parts` = (DiscreteDenoiser, network): the pieces `denoiser` applies, for the fused path."""
@@ -487,18 +290,20 @@ class _KSampler:
         sh = self.discretization(n, device="cpu").float()
         uc = cond if uc is None else uc
         x = x * float(torch.sqrt(1.0 + sh[0] ** 2.0))
-        if self.fused_ok(x, parts):
-            return self._fused(parts[0], parts[1], x.contiguous(), cond, uc, sh)
-        return self._loop(denoiser, x, cond, uc, sh)
+        fused = self.fused_ok(x, parts)
+        if fused:
+            model = _DiscreteEvals(parts[0], parts[1], self.guider.cat_cond(cond, uc), self.guider.scale)
+        else:
+            model = lambda xin, sigma: self.denoise(xin, denoiser, sigma, cond, uc)  # noqa: E731
+        return run_plan(model, x, self.plan(sh, x.shape[0]), fused=fused)
 
-    @staticmethod
-    def _sig(v: float, x):
-        """A [b] sigma vector on x's device holding the fp32 value v (s_in * sigma)."""
-        return torch.full((x.shape[0],), v, dtype=torch.float32, device=x.device)
 
-    @staticmethod
-    def _to_d(x, sigma, denoised):
-        return (x - denoised) / append_dims(sigma, x.ndim)  # sampling_utils.py:42-43
+class DPMPP2MSampler(_KSampler):
+    """sampling.py:29-137,459-573: DPM++ 2M (multistep, second order) with CFG, Cremage's default SDXL sampler (preferences.py:159);
+    fused step: crg_cfg_dpmpp2m_step."""
+
+    def plan(self, sh, b):
+        return plan_dpmpp_2m(sh)
 
 
 class HeunEDMSampler(_KSampler):
@@ -510,44 +315,8 @@ class HeunEDMSampler(_KSampler):
         super().__init__(num_steps, guider, device, fused)
         self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
 
-    def _churn(self, x, r):
-        if r["churn"] is None:
-            return x
-        eps = torch.randn_like(x) * self.s_noise
-        return x + eps * r["churn"]
-
-    def _loop(self, denoiser, x, cond, uc, sh):
-        for r in edm_table(sh, x.shape[0], self.s_churn, self.s_tmin, self.s_tmax):
-            x = self._churn(x, r)
-            sigma_hat = self._sig(r["sigma_hat"], x)
-            denoised = self.denoise(x, denoiser, sigma_hat, cond, uc)
-            d = self._to_d(x, sigma_hat, denoised)
-            euler_step = x + r["dt"] * d
-            if not r["two_call"]:
-                x = euler_step
-                continue
-            nxt = self._sig(r["next"], x)
-            denoised = self.denoise(euler_step, denoiser, nxt, cond, uc)
-            d_new = self._to_d(euler_step, nxt, denoised)
-            d_prime = (d + d_new) / 2.0
-            x = x + d_prime * r["dt"]
-        return x
-
-    def _fused(self, dd, network, x, cond, uc, sh):
-        from .. import ops
-        rows = edm_table(sh, x.shape[0], self.s_churn, self.s_tmin, self.s_tmax)
-        ev = [v for r in rows for v in ([r["sigma_hat"], r["next"]] if r["two_call"] else [r["sigma_hat"]])]
-        evals = _FusedEvals(dd, network, torch.tensor(ev, dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
-        x2, d = torch.empty_like(x), torch.empty_like(x)
-        cfg = self.guider.scale
-        for r in rows:
-            x = self._churn(x, r).contiguous()
-            eps2, c_out = evals(x)
-            ops.cfg_sampler_step_("heun_1", x, eps2, c_out, cfg, sigma=r["sigma_hat"], dt=r["dt"], x2=x2, d=d, one_call=not r["two_call"])
-            if r["two_call"]:
-                eps2, c_out = evals(x2)
-                ops.cfg_sampler_step_("heun_2", x, eps2, c_out, cfg, sigma=r["next"], dt=r["dt"], x2=x2, d=d)
-        return x
+    def plan(self, sh, b):
+        return plan_heun(sh, s_noise=self.s_noise, b=b, s_churn=self.s_churn, s_tmin=self.s_tmin, s_tmax=self.s_tmax, sgm=True)
 
 
 class _AncestralSampler(_KSampler):
@@ -558,75 +327,25 @@ class _AncestralSampler(_KSampler):
         super().__init__(num_steps, guider, device, fused)
         self.eta, self.s_noise = eta, s_noise
 
-    def _ancestral_step(self, x, r):
-        noise = torch.randn_like(x)
-        return x + noise * self.s_noise * r["sigma_up"] if r["next"] > 0.0 else x
-
 
 class EulerAncestralSampler(_AncestralSampler):
     """sampling.py:361-381: an Euler step to sigma_down, then noise of std sigma_up."""
 
-    def _loop(self, denoiser, x, cond, uc, sh):
-        for r in ancestral_table(sh, x.shape[0], self.eta, multipliers=False):
-            sigma = self._sig(r["sigma"], x)
-            denoised = self.denoise(x, denoiser, sigma, cond, uc)
-            x = x + r["dt"] * self._to_d(x, sigma, denoised)
-            x = self._ancestral_step(x, r)
-        return x
-
-    def _fused(self, dd, network, x, cond, uc, sh):
-        from .. import ops
-        rows = ancestral_table(sh, x.shape[0], self.eta, multipliers=False)
-        evals = _FusedEvals(dd, network, torch.tensor([r["sigma"] for r in rows], dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
-        for r in rows:
-            eps2, c_out = evals(x)
-            noise = torch.randn_like(x)
-            ops.cfg_sampler_step_("euler_a", x, eps2, c_out, self.guider.scale, sigma=r["sigma"], dt=r["dt"], noise=noise,
-                                  sigma_up=r["sigma_up"], s_noise=self.s_noise, add_noise=r["next"] > 0.0)
-        return x
+    def plan(self, sh, b):
+        return plan_euler_a(sh, self.eta, self.s_noise, b=b, sgm=True)
 
 
 class DPMPP2SAncestralSampler(_AncestralSampler):
     """sampling.py:384-456: DPM++ 2S ancestral - a second UNet call at the midpoint sigma to_sigma(s) (off the denoiser's grid: it is
     snapped for the scalings only), then noise of std sigma_up; a step whose sigma_down is 0 makes one call (the Euler step)."""
 
-    def _loop(self, denoiser, x, cond, uc, sh):
-        for r in ancestral_table(sh, x.shape[0], self.eta):
-            sigma = self._sig(r["sigma"], x)
-            denoised = self.denoise(x, denoiser, sigma, cond, uc)
-            if not r["two_call"]:
-                x = x + r["dt"] * self._to_d(x, sigma, denoised)
-            else:
-                m1, m2, m3, m4 = r["m"]
-                x2 = m1 * x - m2 * denoised
-                denoised2 = self.denoise(x2, denoiser, self._sig(r["s_sigma"], x), cond, uc)
-                x = m3 * x - m4 * denoised2
-            x = self._ancestral_step(x, r)
-        return x
-
-    def _fused(self, dd, network, x, cond, uc, sh):
-        from .. import ops
-        rows = ancestral_table(sh, x.shape[0], self.eta)
-        ev = [v for r in rows for v in ([r["sigma"], r["s_sigma"]] if r["two_call"] else [r["sigma"]])]
-        evals = _FusedEvals(dd, network, torch.tensor(ev, dtype=torch.float32), x, self.guider.cat_cond(cond, uc))
-        x2 = torch.empty_like(x)
-        cfg = self.guider.scale
-        for r in rows:
-            eps2, c_out = evals(x)
-            noisy = dict(sigma_up=r["sigma_up"], s_noise=self.s_noise, add_noise=r["next"] > 0.0)
-            if not r["two_call"]:
-                ops.cfg_sampler_step_("dpmpp2s_1", x, eps2, c_out, cfg, sigma=r["sigma"], dt=r["dt"], noise=torch.randn_like(x),
-                                      one_call=True, **noisy)
-                continue
-            ops.cfg_sampler_step_("dpmpp2s_1", x, eps2, c_out, cfg, x2=x2, m=r["m"])
-            eps2, c_out = evals(x2)
-            ops.cfg_sampler_step_("dpmpp2s_2", x, eps2, c_out, cfg, x2=x2, m=r["m"], noise=torch.randn_like(x), **noisy)
-        return x
+    def plan(self, sh, b):
+        return plan_dpmpp_2s_a(sh, self.eta, self.s_noise, b=b, sgm=True)
 
 
 class LinearMultistepSampler(_KSampler):
-    """sampling.py:271-306: linear multistep of the given order over the last derivatives (coefficients: lms_table).  The fused path
-    keeps the derivatives in a ring of `order` device buffers and covers order <= 4; a larger order runs the torch loop."""
+    """sampling.py:271-306: linear multistep of the given order over the last derivatives (coefficients: lms_table).  The fused step
+    reads at most three earlier derivatives, so it covers order <= 4; a larger order runs the torch executor."""
 
     FUSED_MAX_ORDER = 4
 
@@ -639,28 +358,8 @@ class LinearMultistepSampler(_KSampler):
     def fused_ok(self, x, parts) -> bool:
         return self.order <= self.FUSED_MAX_ORDER and super().fused_ok(x, parts)
 
-    def _loop(self, denoiser, x, cond, uc, sh):
-        ds = []
-        for i, coeffs in enumerate(lms_table(sh, self.order)):
-            sigma = self._sig(float(sh[i]), x)
-            denoised = self.denoise(x, denoiser, sigma, cond, uc)
-            ds.append(self._to_d(x, sigma, denoised))
-            if len(ds) > self.order:
-                ds.pop(0)
-            x = x + sum(coeff * d for coeff, d in zip(coeffs, reversed(ds)))
-        return x
-
-    def _fused(self, dd, network, x, cond, uc, sh):
-        from .. import ops
-        table = lms_table(sh, self.order)
-        evals = _FusedEvals(dd, network, sh[:-1].clone(), x, self.guider.cat_cond(cond, uc))
-        ring = [torch.empty_like(x) for _ in range(self.order)]
-        for i, coeffs in enumerate(table):
-            eps2, c_out = evals(x)
-            hist = [ring[(i - k) % self.order] for k in range(1, len(coeffs))]
-            ops.cfg_sampler_step_("lms", x, eps2, c_out, self.guider.scale, sigma=float(sh[i]), d=ring[i % self.order], hist=hist,
-                                  coef=coeffs)
-        return x
+    def plan(self, sh, b):
+        return plan_lms(sh, order=self.order)
 
 
 SGM_SAMPLERS = {"euler_edm": EulerEDMSampler, "dpmpp2m": DPMPP2MSampler, "heun_edm": HeunEDMSampler,
@@ -721,7 +420,7 @@ class DiffusionEngine(nn.Module):
     def run_sampler(self, smp, x, cond: Dict, uc: Dict):
         """sampler(denoiser, x, cond=c, uc=uc) (sdxl_image_generator_utils.py:703-707, :1016)."""
         denoiser = lambda inp, sigma, c: self.denoiser(self.model, inp, sigma, c)  # noqa: E731
-        if isinstance(smp, (DPMPP2MSampler, _KSampler)):
+        if isinstance(smp, _KSampler):
             return smp(denoiser, x, cond=cond, uc=uc, parts=(self.denoiser, self.model))
         return smp(denoiser, x, cond=cond, uc=uc)
 

@@ -186,3 +186,51 @@ def test_sampler_step_struct_matches_header():
                                                     "DPMPP2S_1": _lib.STEP_DPMPP2S_1, "DPMPP2S_2": _lib.STEP_DPMPP2S_2,
                                                     "LMS": _lib.STEP_LMS}
     assert "crg_cfg_sampler_step" in _lib.SIGNATURES
+
+
+def _toy_run(smp, B=2, tag="plan"):
+    """The sampler's torch path under the toy denoiser -> (latents, the evaluation sigmas in call order)."""
+    c, uc = {"vector": synth_input(tag + ".cv", (B, 4), 5)}, {"vector": synth_input(tag + ".ucv", (B, 4), 5)}
+    ev = []
+
+    def rec(inp, sigma, cc):
+        ev.append(sigma[0].clone())
+        return toy_denoiser(inp, sigma, cc)
+    return smp(rec, synth_input(tag + ".x0", (B, 4, 5, 3), 5), cond=c, uc=uc), ev
+
+
+def test_plan_samplers_run_through_shared_run_plan(monkeypatch):
+    """Every SDXL sampler but EulerEDM is one call of the run_plan that the SD1.5 samplers run through as well."""
+    from cremage_amd import sampler_plan, samplers
+    from cremage_amd.sgm_hip import sampling as S
+    assert S.run_plan is sampler_plan.run_plan is samplers.run_plan
+    seen = []
+    monkeypatch.setattr(S, "run_plan", lambda *a, **k: seen.append(len(a[2])) or sampler_plan.run_plan(*a, **k))
+    eng = _engine()
+    for key in S.SGM_SAMPLERS:
+        del seen[:]
+        x, ev = _toy_run(eng.make_sampler(key, 4, 5.0, "cpu"))
+        assert torch.isfinite(x).all(), key
+        assert seen == ([] if key == "euler_edm" else [len(ev)]), (key, seen)  # one plan entry per evaluation
+
+
+@pytest.mark.parametrize("s_tmin", [0.0, 1.0])
+def test_heun_churn_on_pruned_schedule(monkeypatch, s_tmin):
+    """HeunEDM with churn on a Txt2Noisy-pruned EDM schedule, which does not end at 0 (the last step makes two evaluations as well):
+    one randn_like draw per step with gamma > 0 and no other, and the evaluation sigmas are edm_table's sigma_hat / next sequence bit
+    for bit.  s_tmin 1.0 leaves the last steps without churn."""
+    from cremage_amd.sgm_hip.sampling import edm_table
+    steps, B, churn = 10, 2, 1.0
+    opts = dict(EDM, sampler_s_churn=churn, sampler_s_noise=0.9, sampler_s_tmin=s_tmin)
+    smp = _engine().make_sampler("heun_edm", steps, 5.0, "cpu", discretization="edm", options=opts, stage2strength=0.5)
+    sh = smp.discretization(steps)
+    assert 2 < len(sh) < steps + 1 and sh[-1] > 0
+    with_gamma = sum(1 for s in sh[:-1].tolist() if s_tmin <= s <= smp.s_tmax and min(churn / (len(sh) - 1), 2 ** 0.5 - 1) > 0)
+    assert with_gamma == (len(sh) - 1 if s_tmin == 0.0 else int((sh[:-1] >= 1.0).sum())) and with_gamma > 0
+    with recorded_noise(monkeypatch, "heun.pruned", 5) as draws:
+        x, ev = _toy_run(smp, B)
+    assert torch.isfinite(x).all()
+    assert len(draws) == with_gamma
+    rows = edm_table(sh, B, churn, s_tmin, smp.s_tmax)
+    assert all(r["two_call"] for r in rows) and sum(r["churn"] is not None for r in rows) == with_gamma
+    assert torch.equal(torch.stack(ev), torch.tensor([v for r in rows for v in (r["sigma_hat"], r["next"])], dtype=torch.float32))

@@ -290,3 +290,39 @@ def test_sdxl_img2img_and_pruned_base_stage(monkeypatch):
                                  unfused, _expected_kinds("heun_edm", n_steps, t2n=True))
     close(fused, g["x_t2n"], TOL_TRAJ, "pruned base heun edm (fused)")
     close(unf, g["x_t2n"], TOL_TRAJ, "pruned base heun edm (unfused)")
+
+
+def _fused_vs_unfused(monkeypatch, key, opts, expect, tag):
+    """6 steps of `key` on the legacy schedule with `opts` on the tiny engine: fused against unfused with the same recorded noise
+    within 1e-5 relative, the fused launches `expect`; returns the two runs' draw counts."""
+    meta, _ = load_golden(f"traj_sdxl_{key}")
+    eng = _tiny_engine(meta)
+    B, L, S, seed = meta["B"], meta["L"], meta["S"], meta["seed"]
+    assert S == 6
+    c, uc = _cond(tag, B, seed)
+    x0 = synth_input(tag + ".x0", (B, 4, L, L), seed).to(DEV)
+
+    def unfused():
+        smp = eng.make_sampler(key, S, meta["cfg"], DEV, options=opts)
+        smp.fused = False
+        return eng.run_sampler(smp, x0, c, uc)
+    fused, unf, nf, nu = _run_both(monkeypatch, eng, tag, seed, lambda: eng.sample(x0, c, uc, S, meta["cfg"], sampler=key, options=opts),
+                                   unfused, expect(S))
+    assert torch.isfinite(fused).all()
+    r = rel_l2(fused.cpu(), unf.cpu())
+    print(f"\n[{tag}] fused vs unfused rel-L2 {r:.3e}")
+    assert r <= 1e-5
+    return nf, nu, S
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+def test_sdxl_lms_low_orders_fused(order, monkeypatch):
+    """LinearMultistep below order 4: the fused executor's derivative ring has `order` slots."""
+    _fused_vs_unfused(monkeypatch, "linear_multistep", {"sampler_order": order}, lambda S: [("lms", False)] * S, f"lms.order{order}")
+
+
+def test_sdxl_euler_ancestral_eta_s_noise_fused(monkeypatch):
+    """EulerAncestral with eta 0.5 and s_noise 1.1: the euler_a step with non-default scalars; one draw per step in both paths."""
+    nf, nu, S = _fused_vs_unfused(monkeypatch, "euler_ancestral", {"sampler_eta": 0.5, "sampler_s_noise": 1.1},
+                                  lambda S: _expected_kinds("euler_ancestral", S), "euler_a.eta05")
+    assert nf == nu == S
