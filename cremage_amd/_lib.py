@@ -157,6 +157,24 @@ class BlendArgs(C.Structure):
     ]
 
 
+MX8_OUT_HALF, MX8_OUT_F32, MX8_OUT_MX8 = 0, 1, 2  # enum crg_mx8_out
+
+
+class Mx8GemmArgs(C.Structure):
+    _fields_ = [
+        ("a_q", c_void_p), ("lda", c_int64),
+        ("a_e", c_void_p), ("lde", c_int64),
+        ("w_q", c_void_p), ("w_e", c_void_p),
+        ("bias", c_void_p),
+        ("residual", c_void_p), ("ldr", c_int64),
+        ("y", c_void_p), ("ldy", c_int64),
+        ("y_e", c_void_p), ("ldye", c_int64),
+        ("M", c_int), ("N", c_int), ("K", c_int),
+        ("epilogue", c_int),
+        ("y_kind", c_int),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -220,6 +238,9 @@ SIGNATURES = {
     "crg_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int]),
     "crg_affine_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int,
                                 c_int]),
+    "crg_quant_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int]),
+    "crg_pack_weight_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "crg_gemm_mx8": (c_int, [c_void_p, c_void_p, C.POINTER(Mx8GemmArgs)]),
 }
 
 

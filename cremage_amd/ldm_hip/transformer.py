@@ -119,8 +119,14 @@ class FeedForward(nn.Module):
     """attention.py:119-168 (glu=True is what SD uses, BasicTransformerBlock passes gated_ff=True)."""
 
     def __init__(self, dim, dim_out=None, mult=4, glu=False, dropout=0., lora_ranks: List[int] = None,
-                 lora_weights: List[float] = None):
+                 lora_weights: List[float] = None, precision: Optional[str] = None):
+        """`precision` (not in the reference's signature): None = the input's own precision, as ever; "mx8" = both GEMMs on block-scaled
+        e4m3 operands (ops.linear_mx8) for half-type inputs.  None becomes "mx8" under CRG_FF_MX8=1 (ops.FF_MX8);
+        cremage_amd.set_ff_precision switches a whole model."""
         super().__init__()
+        if precision not in (None, "mx8"):
+            raise ValueError(f"FeedForward: precision {precision!r} (None or 'mx8')")
+        self.precision = precision or ("mx8" if ops.FF_MX8 else None)
         self.lora_ranks = lora_ranks if lora_ranks is not None else []
         self.lora_weights = lora_weights if lora_weights is not None else [1.0] * len(self.lora_ranks)
         inner_dim = int(dim * mult)
@@ -135,6 +141,14 @@ class FeedForward(nn.Module):
 
     def forward(self, x, residual=None, ln: Optional[nn.LayerNorm] = None, out_stats: bool = False):
         """`out_stats`: the result feeds the next block's LayerNorm - its row statistics come out of this launch (ops.linear, row_stats)."""
+        if self.precision == "mx8" and x.dtype == ops.HALF:
+            # LayerNorm -> quantise -> GEGLU projection with an MX8 result -> net[2] + residual: the intermediate never exists in 16 bits.
+            # The MX8 net[2] emits no row statistics: the next LayerNorm's consumer takes its stand-alone routes (ops.ln_linear_auto)
+            w1, w2 = _eff(self.net[0], self.net[0].proj.weight, "proj"), _eff(self, self.net[2].weight, "net_2")
+            if ops.ff_mx8_ok(x, w1, w2):
+                xn = ops.layer_norm(x, ln.weight, ln.bias, ln.eps) if ln is not None else x
+                hq, he = ops.linear_mx8(*ops.quant_mx8(xn), w1, self.net[0].proj.bias, act="geglu", out="mx8")
+                return ops.linear_mx8(hq, he, w2, self.net[2].bias, residual=residual, out="half")
         h = self.net[0](x, ln=ln)
         return ops.linear(h, _eff(self, self.net[2].weight, "net_2"), self.net[2].bias, residual=residual, row_stats=out_stats)
 

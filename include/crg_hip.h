@@ -591,6 +591,40 @@ int crg_blur_blend_u8(crg_ctx* ctx, void* stream, const crg_blend_args* args);
  * ControlNet residual adds, cldm.py:57-65) */
 int crg_axpby(crg_ctx* ctx, void* stream, const void* x, void* y, int64_t n, float a, float b, int dtype);
 
+/* ---- MX8: block-scaled e4m3 operands for the feed-forward GEMMs (opt-in: FeedForward(precision="mx8"), CRG_FF_MX8=1) ------------------
+ * An MX8 matrix of logical shape [R][K], K % 32 == 0, is two byte planes:
+ *   q: uint8 [R][K]       OCP e4m3fn codes (bias 7, no infinities, largest finite 448)
+ *   e: uint8 [R][K / 32]  E8M0: the 32 elements q[r][32 b .. 32 b + 31] are multiplied by s = 2^(e[r][b] - 127)
+ * Scale rule per 32-element block, on the fp32 value of each element, a = the block's largest magnitude:
+ *   a == 0: e = 127 and every code is 0.  Otherwise a = m 2^E with m in [1, 2): e - 127 = E - 8 when m <= 1.75, else E - 7 - the smallest
+ *   power of two with a / s <= 448, so nothing clips - and e is clamped to [0, 254].  Codes are x / s rounded to nearest-even into e4m3,
+ *   saturating at +-448 (reachable only where e was clamped); a value that rounds to zero has code 0 whatever its sign.  Inputs are
+ *   finite.  ops.quant_mx8_host restates the rule in plain torch; the kernels are bit-exact to it.
+ * crg_quant_mx8: x = [M][K] of the library's half type with row stride ldx (elements; any alignment) -> q [M][K], e [M][K / 32], dense.
+ * crg_pack_weight_mx8: a Linear weight src [n_out][n_in] (fp32 / bf16 / fp16, dense) -> the planes the GEMM reads: q [n_out][n_in] and
+ *   e [n_out][n_in / 32] in the row order of crg_pack_weight (CRG_PACK_LINEAR: as is; CRG_PACK_GEGLU: value / gate rows interleaved in
+ *   16-row groups, n_out % 32 == 0); the rule runs along n_in.
+ * crg_gemm_mx8: Y = epi(A W^T + bias) (+ residual) on v_mfma_scale_f32_16x16x128_f8f6f4, every 32-element block of either operand under
+ *   its own scale, fp32 accumulation.  M >= 1 arbitrary; K % 64 == 0; N % 32 == 0 (rows of W, before the GEGLU halving).  Anything else is
+ *   an error (-22): there is no fallback.  Not offered: batch, split-K, transposed ranges, GroupNorm / LayerNorm statistics.
+ * Profile slots: the GEMM counts under CRG_K_GEMM_W1 (family "gemm"), the quantisers under CRG_K_ELEMENTWISE. */
+enum crg_mx8_out { CRG_MX8_OUT_HALF = 0, CRG_MX8_OUT_F32 = 1, CRG_MX8_OUT_MX8 = 2 };
+typedef struct {
+  const void* a_q; int64_t lda;      /* uint8 [M][lda]; 16-byte aligned rows */
+  const void* a_e; int64_t lde;      /* uint8 [M][lde] */
+  const void* w_q; const void* w_e;  /* crg_pack_weight_mx8: [N][K], [N][K / 32] */
+  const float* bias;                 /* fp32 [N] or NULL (GEGLU: crg_pack_geglu_bias) */
+  const void* residual; int64_t ldr; /* half type [M][ldr] or NULL; CRG_EPI_NONE only */
+  void* y; int64_t ldy;              /* y_kind HALF: half type, F32: float, MX8: uint8 codes; [M][ldy], ldy % 4 == 0, 16-byte aligned base */
+  void* y_e; int64_t ldye;           /* y_kind MX8: uint8 [M][ldye] scales; the output width must be a multiple of 64 then */
+  int M, N, K;
+  int epilogue;                      /* CRG_EPI_NONE | CRG_EPI_GEGLU (erf form; the output is [M][N / 2]) */
+  int y_kind;                        /* enum crg_mx8_out */
+} crg_mx8gemm_args;
+int crg_quant_mx8(crg_ctx* ctx, void* stream, const void* x, int64_t ldx, void* q, void* e, int64_t M, int K);
+int crg_pack_weight_mx8(crg_ctx* ctx, void* stream, const void* src, int src_dtype, int kind, int n_out, int n_in, void* dst_q, void* dst_e);
+int crg_gemm_mx8(crg_ctx* ctx, void* stream, const crg_mx8gemm_args* args);
+
 #ifdef __cplusplus
 }
 #endif
