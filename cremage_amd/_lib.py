@@ -175,6 +175,17 @@ class Mx8GemmArgs(C.Structure):
     ]
 
 
+class AttnX3Args(C.Structure):
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_int64),
+        ("k", c_void_p), ("ldk", c_int64),
+        ("vt", c_void_p), ("ldvt", c_int64),
+        ("o", c_void_p), ("ldo", c_int64),
+        ("B", c_int), ("H", c_int), ("Nq", c_int), ("Nk", c_int), ("Dh", c_int),
+        ("scale", c_float),
+    ]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -241,6 +252,7 @@ SIGNATURES = {
     "crg_quant_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int]),
     "crg_pack_weight_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "crg_gemm_mx8": (c_int, [c_void_p, c_void_p, C.POINTER(Mx8GemmArgs)]),
+    "crg_attention_x3": (c_int, [c_void_p, c_void_p, C.POINTER(AttnX3Args)]),
 }
 
 

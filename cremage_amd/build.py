@@ -14,12 +14,14 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libcrg_hip.so")
 LIB_F16 = os.path.join(HERE, "libcrg_hip_f16.so")  # the same sources with -DCRG_F16_BUILD: fp16 operands (crg_common.h)
-SOURCES = ["crg_api.hip", "gemm_conv.hip", "conv_pp.hip", "gemm_ring.hip", "lngemm.hip", "norms.hip", "attention.hip", "small_ops.hip", "poisson.hip", "blur_blend.hip", "mx8.hip"]
+SOURCES = ["crg_api.hip", "gemm_conv.hip", "conv_pp.hip", "gemm_ring.hip", "lngemm.hip", "norms.hip", "attention.hip", "small_ops.hip", "poisson.hip", "blur_blend.hip", "mx8.hip", "attention_x3.hip"]
 HEADERS = [os.path.join(CSRC, "crg_common.h"), os.path.join(CSRC, "gemm_shared.h"), os.path.join(HERE, "..", "include", "crg_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # attention.hip: without NaN-honouring semantics fmaxf lowers to plain v_max_f32 / v_max3_f32 instead of a canonicalising
 # v_max per MFMA output (32 extra VALU per 64-key tile in a VALU-bound loop).  Infinities (the -inf key mask) are kept.
-EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans"]}
+# attention_x3.hip: the compiler's resource report is read back and held against the kernel's budget (_check_budget).
+EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans"], "attention_x3.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+BUDGET_CHECKED = {"attention_x3.hip"}  # no scratch, at most 512 registers per lane (VGPR + AGPR); the LDS bound is a static_assert
 
 
 def _hipcc():
@@ -33,6 +35,17 @@ def _newer(a, b):
     return (not os.path.exists(b)) or os.path.getmtime(a) > os.path.getmtime(b)
 
 
+def _check_budget(src, report):
+    """Every kernel of `src`: ScratchSize 0 and VGPRs + AGPRs <= 512, from -Rpass-analysis=kernel-resource-usage."""
+    import re
+    kernels = re.findall(r"Function Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+)", report, re.S)
+    if not kernels:
+        raise RuntimeError(f"{src}: the compiler printed no resource report")
+    for name, vgpr, agpr, scratch in kernels:
+        if int(scratch) != 0 or int(vgpr) + int(agpr) > 512:
+            raise RuntimeError(f"{src}: {name} is over budget: {vgpr} VGPRs + {agpr} AGPRs, {scratch} B of scratch per lane")
+
+
 def _compile(job):
     src, f16 = job
     s = os.path.join(CSRC, src)
@@ -43,6 +56,12 @@ def _compile(job):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-4000:]}")
+    if src in BUDGET_CHECKED:
+        try:
+            _check_budget(src, r.stderr)
+        except RuntimeError:
+            os.remove(o)  # or the next build would find the object up to date and link it
+            raise
     return o, True
 
 

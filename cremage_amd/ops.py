@@ -1151,14 +1151,48 @@ def image_of_stats(t: torch.Tensor, h: int, w: int) -> torch.Tensor:
 SCORE_BUDGET_BYTES = 256 << 20  # fp32 score buffer of the unfused attention path (queries are processed in chunks that fit it)
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_keys: int, scale: float) -> torch.Tensor:
+# CRG_ATTN_X3=1 sends fp32 attention through the flash kernel of the class (crg_attention_x3: one launch, no score buffer) wherever
+# attention_x3_ok holds - a knob like CRG_VAE_MX / CRG_FF_MX8, off by default.  Read per call of `attention`, i.e. at CAPTURE time
+# for a captured graph: a replay runs what was captured (graphs.py).
+ATTN_X3_FLASH = _env.get("CRG_ATTN_X3", "0") != "0"
+
+
+def _attention_x3_why_not(q, k, vt, heads):
+    """The violated condition of the fp32 flash kernel's domain, or None."""
+    for name, t in (("q", q), ("k", k), ("vt", vt)):
+        if not t.is_cuda:
+            return f"{name} does not live on a HIP device"
+        if t.dtype != torch.float32:
+            return f"{name} is {t.dtype}, the kernel takes float32 only"
+    if q.dim() != 3 or heads <= 0 or q.shape[2] % heads:
+        return f"q {tuple(q.shape)} does not split into {heads} heads"
+    dh = q.shape[2] // heads
+    if dh % 8 or not 8 <= dh <= 512:
+        return f"head dim {dh} is not a multiple of 8 in 8 .. 512"
+    return None
+
+
+def attention_x3_ok(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_keys: int) -> bool:
+    """True where `attention(..., flash=True)` is defined: fp32 tensors on the device, d_head a multiple of 8 up to 512."""
+    return n_keys > 0 and _attention_x3_why_not(q, k, vt, heads) is None
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_keys: int, scale: float,
+              flash: Optional[bool] = None) -> torch.Tensor:
     """softmax(Q K^T * scale) V with heads split along the channel dim.
     q: [B, Nq, C], k: [B, Nk, C], vt: [B, C, ld] (V transposed, ld = roundup(Nk, 8)) -> [B, Nq, C].
     Pad columns n_keys..ld of vt: the flash branch (half type, d_head <= 160) masks keys >= n_keys and never reads them unmasked, so
     anything may sit there.  The unfused branch (fp32, or d_head > 160) does NOT mask: its PV GEMM runs over roundup(n_keys, 8)
     columns and multiplies the pads by the score buffer's pad columns, which are exact zeros - finite pads drop out bitwise,
     non-finite ones (NaN, inf) would poison every output.  Every producer in this module (`linear_transposed`, `linear` /
-    `ln_linear` with transposed_from) zeroes them; a caller that builds vt itself must do the same."""
+    `ln_linear` with transposed_from) zeroes them; a caller that builds vt itself must do the same.
+    flash (fp32 inputs only; half-type inputs ignore it): True = the fp32-class flash kernel (crg_attention_x3) or a CrgError naming
+    the violated condition; False = the unfused branch; None = the flash kernel when ATTN_X3_FLASH is set and attention_x3_ok holds,
+    else the unfused branch.  The flash kernel masks keys >= n_keys like the half-type one and needs only n_keys columns of vt."""
+    if flash and q.dtype != HALF:
+        why = _attention_x3_why_not(q, k, vt, heads)
+        if why is not None:
+            raise L.CrgError(f"attention(flash=True): {why}")
     _need_cuda(q, k, vt)
     if q.dim() != 3 or k.dim() != 3 or vt.dim() != 3:
         raise L.CrgError("attention: q [B, Nq, C], k [B, Nk, C] and vt [B, C, ld] expected")
@@ -1172,6 +1206,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
     if not 0 < n_keys <= min(k.shape[1], vt.shape[-1]):
         raise L.CrgError(f"attention: n_keys = {n_keys} outside k's {k.shape[1]} rows / vt's {vt.shape[-1]} columns")
     Dh = Cc // heads
+    if q.dtype == torch.float32 and (flash if flash is not None else ATTN_X3_FLASH and attention_x3_ok(q, k, vt, heads, n_keys)):
+        return _attention_x3(q, k, vt, heads, n_keys, scale)
     flash = q.dtype == HALF and Dh <= 160
     if not flash and vt.shape[-1] < (n_keys + 7) // 8 * 8:
         raise L.CrgError(f"attention: the unfused branch reads roundup(n_keys, 8) columns of vt, which has {vt.shape[-1]} for {n_keys} keys")
@@ -1231,6 +1267,27 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
                   w_bstride=Dh * ld, bias=None, bias_mode=L.BIAS_NONE, residual=None, ldr=0, r_bstride=0, y=o[b, q0:].data_ptr(), ldy=Cc,
                   y_bstride=Dh, M=nq, N=Dh, K=kp, batch=heads, epilogue=L.EPI_NONE, a_dtype=L.F32, y_dtype=_act_dt(q), prec=prec,
                   a_is_weight=0, a_lo=None)
+    return o
+
+
+def _attention_x3(q, k, vt, heads, n_keys, scale):
+    """The fp32-class flash route of `attention` (arguments already checked there)."""
+    B, Nq, Cc = q.shape
+    k = k[:, :n_keys]
+
+    def rows(t):  # column slices keep their parent's row stride; the kernel wants 16-byte aligned rows one batch stride apart
+        if (t.stride(2) != 1 or t.stride(1) % 4 or t.stride(1) < Cc or t.data_ptr() % 16
+                or (B > 1 and t.stride(0) != t.shape[1] * t.stride(1))):
+            t = t.contiguous()
+        return t, t.stride(1)
+    q, ldq = rows(q)
+    k, ldk = rows(k)
+    vt = vt.contiguous()  # no-op for the [B, C, ld] every producer of this module returns
+    o = torch.empty((B, Nq, Cc), dtype=torch.float32, device=q.device)
+    h = _h(q)
+    a = L.AttnX3Args(q=q.data_ptr(), ldq=ldq, k=k.data_ptr(), ldk=ldk, vt=vt.data_ptr(), ldvt=vt.shape[-1], o=o.data_ptr(), ldo=Cc,
+                     B=B, H=heads, Nq=Nq, Nk=n_keys, Dh=Cc // heads, scale=scale)
+    L.check(L.load().crg_attention_x3(h, _st(), C.byref(a)), h, "crg_attention_x3")
     return o
 
 

@@ -625,6 +625,29 @@ int crg_quant_mx8(crg_ctx* ctx, void* stream, const void* x, int64_t ldx, void* 
 int crg_pack_weight_mx8(crg_ctx* ctx, void* stream, const void* src, int src_dtype, int kind, int n_out, int n_in, void* dst_q, void* dst_e);
 int crg_gemm_mx8(crg_ctx* ctx, void* stream, const crg_mx8gemm_args* args);
 
+/* ---- flash attention for the fp32 class (opt-in: ops.attention(..., flash=True), CRG_ATTN_X3=1) ------------------------------------------
+ * O = softmax(Q K^T * scale) V on fp32 tensors in ONE launch for all batches, heads and query blocks.  Replaces, for fp32 inputs, the
+ * host loop of the unfused route: per image and query chunk a hi / lo split of K and V^T, a batched QK^T GEMM into an fp32 score buffer,
+ * the row softmax and a batched PV GEMM.  Here the hi / lo planes of Q, K, V and P are made inside the kernel (registers / LDS), there is
+ * no plane tensor, no score buffer and no workspace: memory does not grow with Nq x Nk.
+ *   q  fp32 [B][Nq][ldq], head h at column h*Dh      k fp32 [B][Nk][ldk]      (q and k may be column slices of one projection output)
+ *   vt fp32 [B][H*Dh][ldvt]: V transposed            o fp32 [B][Nq][ldo]
+ * Arithmetic of the class: S = Qh Kh + Qh Kl + Ql Kh and O += Ph Vh + Ph Vl + Pl Vh on the half-type MFMA with fp32 accumulation;
+ * running max, exp, row sum and rescale in fp32.  Keys >= Nk are masked by selection and their memory is never read: rows of k past Nk
+ * and columns Nk..ldvt of vt may hold anything, NaN included.  Bitwise deterministic (no atomics, no key split).
+ * Domain: Dh % 8 == 0, 8 <= Dh <= 512; Nq >= 1; 1 <= Nk <= ldvt; B, H in 1..65535; ldq, ldk, ldo >= H*Dh and multiples of 4 with
+ * 16-byte aligned q, k, o; vt 4-byte aligned with any ldvt (rows are read as float4 when ldvt % 4 == 0 and vt is 16-byte aligned).
+ * Anything else is an error (-22): there is no fallback.  Profile slot: CRG_K_ATTN. */
+typedef struct {
+  const float* q; int64_t ldq;
+  const float* k; int64_t ldk;
+  const float* vt; int64_t ldvt;
+  float* o; int64_t ldo;
+  int B, H, Nq, Nk, Dh;
+  float scale;
+} crg_attn_x3_args;
+int crg_attention_x3(crg_ctx* ctx, void* stream, const crg_attn_x3_args* args);
+
 #ifdef __cplusplus
 }
 #endif
