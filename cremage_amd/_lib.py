@@ -186,6 +186,15 @@ class AttnX3Args(C.Structure):
     ]
 
 
+ROUTE_KERNELS = ["none", "glds", "rowhalo", "conv_pp", "gemm_ring", "gemm_reg", "planes"]  # enum crg_route_kernel
+ROUTE_REDUCES = ["none", "plain", "stats", "rows", "gn"]  # enum crg_route_reduce
+
+
+class Route(C.Structure):
+    _fields_ = [("kernel", c_int), ("wnt", c_int), ("config", c_int), ("splits", c_int), ("tail_splits", c_int), ("rowhalo", c_int),
+                ("halo_lin", c_int), ("pair", c_int), ("up2", c_int), ("mx", c_int), ("reduce", c_int), ("gn_stats_rows", c_int)]
+
+
 class Profile(C.Structure):
     _fields_ = [("ms", C.c_double * K_SLOTS), ("flops", C.c_double * K_SLOTS), ("bytes", C.c_double * K_SLOTS),
                 ("launches", C.c_int64 * K_SLOTS)]
@@ -218,6 +227,7 @@ SIGNATURES = {
     "crg_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_int]),
     "crg_gemm": (c_int, [c_void_p, c_void_p, C.POINTER(GemmArgs)]),
     "crg_conv2d": (c_int, [c_void_p, c_void_p, C.POINTER(ConvArgs)]),
+    "crg_last_route": (c_int, [c_void_p, C.POINTER(Route)]),
     "crg_ln_gemm": (c_int, [c_void_p, c_void_p, C.POINTER(LnGemmArgs)]),
     "crg_pack_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "crg_pack_geglu_bias": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -278,8 +288,8 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.crg_version() != 103:
-        raise CrgError(f"libcrg_hip.so version {lib.crg_version()} does not match the binding (103)")
+    if lib.crg_version() != 104:
+        raise CrgError(f"libcrg_hip.so version {lib.crg_version()} does not match the binding (104)")
     if lib.crg_half_kind() != (1 if HALF_F16 else 0):
         raise CrgError(f"{LIB_PATH} computes in {'fp16' if lib.crg_half_kind() else 'bf16'} but CRG_HALF asks for {'fp16' if HALF_F16 else 'bf16'}")
     _lib = lib

@@ -80,6 +80,11 @@ extern "C" void crg_ctx_destroy(crg_ctx* ctx) {
 }
 
 extern "C" const char* crg_last_error(crg_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
+extern "C" int crg_last_route(crg_ctx* ctx, crg_route* out) {
+  if (!ctx || !out) return -22;
+  *out = ctx->route;
+  return 0;
+}
 
 extern "C" int crg_ctx_reserve(crg_ctx* ctx, size_t bytes) {
   if (!ctx) return -22;

@@ -1522,6 +1522,7 @@ int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, int batch) {
     }
     CRG_CHECK_LAUNCH(ctx, "splitk_reduce_gn");
     ctx->gn_fused = true;
+    ctx->route.reduce = CRG_REDUCE_GN;
     return 0;
   }
   if (p.rstat) {
@@ -1529,14 +1530,17 @@ int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, int batch) {
       return crg_fail(ctx, -22, "gemm: LayerNorm row statistics behind split-K need an unbatched plain bf16 problem with 4-aligned N / ldy / ldr");
     const long blocks = (rows + 3) / 4;
     hipLaunchKernelGGL(splitk_reduce_rows_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, p);
+    ctx->route.reduce = CRG_REDUCE_ROWS;
   } else if (p.gstat) {
     if (batch != 1 || (p.N & 3) || (p.ldy & 3) || (p.slab_row0 & 31) || (p.res && (p.ldr & 3)))
       return crg_fail(ctx, -22, "gemm: GroupNorm statistics need an unbatched problem with 4-aligned N / ldy / ldr");
     hipLaunchKernelGGL(splitk_reduce_stats_kernel<YT>, dim3((unsigned)((rows + 31) / 32), (unsigned)((p.N + 127) / 128)), dim3(256), 0, st, p);
+    ctx->route.reduce = CRG_REDUCE_STATS;
   } else {
     const long total4 = rows * (p.N >> 2);
     const int rg = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
     hipLaunchKernelGGL(splitk_reduce_kernel<YT>, dim3(rg, batch), dim3(256), 0, st, p);
+    ctx->route.reduce = CRG_REDUCE_PLAIN;
   }
   CRG_CHECK_LAUNCH(ctx, "splitk_reduce");
   return 0;
@@ -1673,11 +1677,26 @@ int launch_kernel(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
                              : (CONV ? (WNT == 5 ? CRG_K_CONV_W5 : WNT == 4 ? CRG_K_CONV_W4 : CRG_K_CONV_W1)
                                      : (WNT == 5 ? CRG_K_GEMM_W5 : WNT == 4 ? CRG_K_GEMM_W4 : CRG_K_GEMM_W1));
   crg_prof_scope ps(ctx, st, slot, wk.flops, wk.bytes);
+  {
+    crg_route& r = ctx->route;  // (the tail split launches twice: `launch` merges the two records)
+    r.kernel = halo ? CRG_ROUTE_ROWHALO : GLDS ? CRG_ROUTE_GLDS : CRG_ROUTE_GEMM_REG;
+    r.wnt = WNT;
+    r.config = !GLDS ? 0 : (KG == 2 ? 3 : WMT == 2 ? 4 : 1);
+    r.splits = p.splits;
+    r.rowhalo = halo ? p.rowhalo : 0;
+    r.halo_lin = halo ? p.halo_lin : 0;
+    r.pair = p.pair;
+    r.up2 = p.up == 2 ? 1 : 0;
+    r.mx = 0;
+    r.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
+  }
   if constexpr (GLDS && CONV && STAGES == 2 && WMT == 4 && KG == 1 && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     if (halo && p.rowhalo == 2 && p.ring) {
       // one statistics partial per 256-pixel tile and channel instead of eight (crg_groupnorm_pre then needs no finalise launch):
       // paired epilogue, no K slices, tiles that do not straddle samples
       if (p.gstat && p.gstat_tile_ok && p.pair && p.splits == 1 && (p.Ho * p.Wo) % 256 == 0) p.gstat_rows = 256;
+      ctx->route.kernel = CRG_ROUTE_CONV_PP;
+      ctx->route.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
       return launch_conv_pp(ctx, st, p, WNT);
     }
   }
@@ -1785,8 +1804,12 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
         p.splits = s2;
         p.slab = slab;
         p.slab_row0 = row0;
+        const int pair1 = ctx->route.pair;
         rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * r / T, wk.bytes * r / T, 0, 0});
         if (rc) return rc;
+        ctx->route.splits = 1;  // the record describes the main launch; of the tail it keeps the K cut
+        ctx->route.pair = pair1;
+        ctx->route.tail_splits = s2;
         return launch_reduce<YT>(ctx, st, p, 1);
       }
     }
@@ -1855,6 +1878,15 @@ int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     crg_prof_scope ps(ctx, st, CONV ? CRG_K_CONV_X3 : CRG_K_GEMM_X3, wk.flops, wk.bytes);
     hipLaunchKernelGGL(kern, dim3(p.tiles_n * p.tiles_m * p.splits, batch, 1), dim3(512), lds_bytes, st, p);
     CRG_CHECK_LAUNCH(ctx, "gemm(planes)");
+    crg_route& r = ctx->route;
+    r.kernel = CRG_ROUTE_PLANES;
+    r.wnt = WNT;
+    r.splits = p.splits;
+    r.rowhalo = halo ? 1 : 0;
+    r.halo_lin = halo ? p.halo_lin : 0;
+    r.up2 = p.up == 2 ? 1 : 0;
+    r.mx = p.mx ? 1 : 0;
+    r.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
   }
   if (p.splits > 1) {
     const long total4 = (long)p.M * (p.N >> 2);
@@ -1862,6 +1894,7 @@ int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     crg_prof_scope ps(ctx, st, CRG_K_SPLITK, (double)batch * p.splits * p.M * p.N, (double)batch * p.M * p.N * (4.0 * p.splits + 4));
     hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(rg, batch), dim3(256), 0, st, p);
     CRG_CHECK_LAUNCH(ctx, "splitk_reduce");
+    ctx->route.reduce = CRG_REDUCE_PLAIN;
   }
   return 0;
 }
@@ -1909,6 +1942,7 @@ int dispatch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, int a_dtype, int
 
 extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
   if (!ctx || !a) return -22;
+  ctx->route = crg_route{};
   CRG_REQUIRE(ctx, a->M > 0 && a->N > 0 && a->K > 0 && a->batch > 0, "gemm: empty problem M=%d N=%d K=%d batch=%d", a->M, a->N, a->K, a->batch);
   CRG_REQUIRE(ctx, a->K % 8 == 0, "gemm: K=%d must be a multiple of 8", a->K);
   const int ae = (a->a_dtype == CRG_F32) ? 4 : 8;  // elements per 16 B
@@ -1966,6 +2000,7 @@ extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
 
 extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   if (!ctx || !a) return -22;
+  ctx->route = crg_route{};
   const int Ctot = a->C1 + a->C2;
   CRG_REQUIRE(ctx, a->N > 0 && a->H > 0 && a->W > 0 && a->Cout > 0 && Ctot > 0, "conv2d: empty problem");
   CRG_REQUIRE(ctx, a->ksize == 3 || a->ksize == 1, "conv2d: ksize %d unsupported", a->ksize);

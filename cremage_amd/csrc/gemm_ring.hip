@@ -550,6 +550,9 @@ int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops,
   crg_prof_scope ps(ctx, st, wnt == 5 ? CRG_K_GEMM_W5 : CRG_K_GEMM_W4, flops, bytes);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
   CRG_CHECK_LAUNCH(ctx, "gemm_ring");
+  ctx->route.kernel = CRG_ROUTE_GEMM_RING;
+  ctx->route.wnt = wnt;
+  ctx->route.splits = 1;
   return 0;
 }
 

@@ -759,6 +759,21 @@ def _gemm(h, **kw):
     L.check(L.load().crg_gemm(h, _st(), C.byref(a)), h, "crg_gemm")
 
 
+def last_route(device: Optional[int] = None) -> dict:
+    """What the last crg_gemm / crg_conv2d call on the device's context decided (crg_last_route, include/crg_hip.h): a plain dict with
+    `kernel` in L.ROUTE_KERNELS, `reduce` in L.ROUTE_REDUCES and the other fields of crg_route as integers.  Host bookkeeping: reads
+    nothing from the device.  linear / linear_transposed / conv1x1 / conv2d set it; the thin-channel convs (crg_conv_small), ln_linear
+    and linear_mx8 have one kernel each and leave it as it was."""
+    idx = torch.cuda.current_device() if device is None else int(device)
+    h = L.ctx(idx)
+    r = L.Route()
+    L.check(L.load().crg_last_route(h, C.byref(r)), h, "crg_last_route")
+    d = {name: int(getattr(r, name)) for name, _ in L.Route._fields_}
+    d["kernel"] = L.ROUTE_KERNELS[d["kernel"]]
+    d["reduce"] = L.ROUTE_REDUCES[d["reduce"]]
+    return d
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
            act: Optional[str] = None, out_dtype: Optional[torch.dtype] = None, gn_hw: Optional[int] = None,
            transposed_from: Optional[int] = None, row_stats: bool = False, ln=None):

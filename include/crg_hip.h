@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CRG_VERSION 103
+#define CRG_VERSION 104
 
 typedef struct crg_ctx crg_ctx;
 
@@ -272,6 +272,44 @@ typedef struct {
   int* gn_stats_rows;
 } crg_conv_args;
 int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* args);
+
+/* ---- route record: which kernel the last crg_gemm / crg_conv2d call on this context ran ---------------
+ * The GEMM / conv dispatcher picks a kernel family, a tile configuration and a K cut from block counts; a test (or a profile) that wants
+ * to know what a shape exercised asks here instead of restating the thresholds.  Both entry points clear the record when they are
+ * entered, so after a call that failed before it launched anything `kernel` is CRG_ROUTE_NONE.  Host bookkeeping only: no launch, no
+ * synchronisation.  crg_ln_gemm, crg_conv_small and crg_gemm_mx8 have one kernel each and leave the record alone. */
+enum crg_route_kernel {
+  CRG_ROUTE_NONE = 0,
+  CRG_ROUTE_GLDS = 1,       /* gemm_glds_kernel, one plane: LDS-DMA GEMM / generic implicit-GEMM conv                                  */
+  CRG_ROUTE_ROWHALO = 2,    /* conv3_rowhalo_kernel, one plane: 3x3 conv on row buffers with a halo                                    */
+  CRG_ROUTE_CONV_PP = 3,    /* conv3_pp_kernel (conv_pp.hip): the staggered 256-pixel-tile 3x3 conv                                    */
+  CRG_ROUTE_GEMM_RING = 4,  /* gemm_ring_kernel (gemm_ring.hip): persistent 256-row tiles                                              */
+  CRG_ROUTE_GEMM_REG = 5,   /* gemm_kernel: register-staged operands (fp32 A, or fp32-class on unsplit operands)                       */
+  CRG_ROUTE_PLANES = 6      /* launch_planes: fp32-class / MX on pre-split planes (gemm_glds_kernel or conv3_rowhalo_kernel, see rowhalo) */
+};
+enum crg_route_reduce {
+  CRG_REDUCE_NONE = 0,
+  CRG_REDUCE_PLAIN = 1,  /* splitk_reduce_kernel        */
+  CRG_REDUCE_STATS = 2,  /* splitk_reduce_stats_kernel  (GroupNorm statistics side channel) */
+  CRG_REDUCE_ROWS = 3,   /* splitk_reduce_rows_kernel   (LayerNorm row statistics)          */
+  CRG_REDUCE_GN = 4      /* splitk_reduce_gn_kernel     (the GroupNorm behind the conv)     */
+};
+typedef struct {
+  int kernel;         /* enum crg_route_kernel */
+  int wnt;            /* tile width / 32: 1, 4 or 5 */
+  int config;         /* tile configuration of the LDS-DMA kernel: 1 = A (128 rows, 4 waves), 3 = C (64 rows, 8 waves in two k-groups),
+                         4 = D (64 rows, 4 waves); 0 where it has no meaning (ring GEMM, register-staged kernel, planes) */
+  int splits;         /* K slices of the (main) launch, 1 = none */
+  int tail_splits;    /* K slices of the tail launch (the last T % 512 tiles, cut along K); 0 = no tail launch */
+  int rowhalo;        /* 0 = not a row-halo kernel, 1 = 128-row tiles, 2 = 256-row tiles */
+  int halo_lin;       /* row-halo kernels: 1 = linear row buffer (output widths that do not tile 128) */
+  int pair;           /* paired 16-bit epilogue of the main launch (LDS-DMA, row-halo and 256-pixel-tile kernels) */
+  int up2;            /* sub-pixel upsample form */
+  int mx;             /* CRG_PREC_F16MX */
+  int reduce;         /* enum crg_route_reduce: the launch that summed the K slices */
+  int gn_stats_rows;  /* rows per partial of the gn_stats side channel this call wrote (32 or 256); 0 = none asked for */
+} crg_route;
+int crg_last_route(crg_ctx* ctx, crg_route* out);
 
 /* ---- weight packing -------------------------------------------------------------------------
  * src: a torch parameter as the checkpoint stores it (fp32/bf16/fp16):

@@ -25,14 +25,14 @@ def test_library_exports_every_declared_symbol():
     for sym in _declared():
         assert hasattr(dll, sym), sym
     assert set(_declared()) == set(_lib.SIGNATURES), set(_declared()) ^ set(_lib.SIGNATURES)
-    assert _lib.load().crg_version() == 103
+    assert _lib.load().crg_version() == 104
 
 
 def test_struct_layouts_match_header():
     """field order of the ctypes structures == field order of the C structs"""
     from cremage_amd import _lib
     header = open(os.path.join(REPO, "include", "crg_hip.h")).read()
-    for cname, cls in [("crg_gemm_args", _lib.GemmArgs), ("crg_conv_args", _lib.ConvArgs)]:
+    for cname, cls in [("crg_gemm_args", _lib.GemmArgs), ("crg_conv_args", _lib.ConvArgs), ("crg_route", _lib.Route)]:
         body = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\} " + cname + ";", header, re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []

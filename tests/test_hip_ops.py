@@ -71,6 +71,15 @@ def nhwc(x, dtype):
 DTYPES = [BF, torch.float32]
 
 
+def assert_route(what, **want):
+    """which kernel the last crg_gemm / crg_conv2d call ran (ops.last_route(): the dispatcher's own record, crg_last_route), held against
+    the route the case is about - a retuned threshold that moves a shape to another kernel fails here instead of passing on it"""
+    from cremage_amd import ops
+    r = ops.last_route()
+    print(f"[route] {what}: " + " ".join(f"{k}={v}" for k, v in r.items()))
+    assert {k: r[k] for k in want} == want, (what, r)
+
+
 # ------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(128, 160, 64), (300, 320, 328), (77, 128, 768), (8, 1280, 320), (1000, 200, 72), (130, 36, 40),
@@ -84,10 +93,21 @@ def test_linear_shapes(dtype, M, N, K):
     from cremage_amd import ops
     x, w, b, r = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5), rnd(N, seed=3), rnd(M, N, seed=4)
     ref = F.linear(q(x, dtype), q(w, BF) if dtype == BF else w, b) + q(r, dtype)
+    # half type: the LDS-DMA kernel in the configuration the shape's comment names (the unnamed small shapes: C); fp32: the register-staged
+    # kernel, which has one configuration, cuts K by the same rule and has no tail split
+    want = {(3000, 1280, 320): dict(config=4, splits=1), (8200, 1280, 136): dict(config=1, splits=1, tail_splits=0),
+            (2048, 640, 1280): dict(config=3, splits=1), (520, 320, 4096): dict(config=1, splits=8, reduce="plain"),
+            (35840, 320, 1024): dict(config=1, splits=1, tail_splits=4, reduce="plain")}.get((M, N, K), dict(config=3, splits=1, reduce="none"))
+    if dtype == BF:
+        want = dict(want, kernel="glds")
+    else:
+        want = dict(kernel="gemm_reg", config=0, splits=want["splits"], tail_splits=0)
     got = ops.linear(x.to(_dev()).to(dtype), w.to(_dev()), b.to(_dev()), residual=r.to(_dev()).to(dtype))
+    assert_route(f"linear {M}x{N}x{K}", **want)
     check(got, ref, dtype, f"linear {M}x{N}x{K}")
     ref2 = F.silu(F.linear(q(x, dtype), q(w, BF) if dtype == BF else w, b))
     got2 = ops.linear(x.to(_dev()).to(dtype), w.to(_dev()), b.to(_dev()), act="silu")
+    assert_route(f"linear+silu {M}x{N}x{K}", **want)
     check(got2, ref2, dtype, "linear+silu")
 
 
@@ -367,14 +387,24 @@ def test_conv2d(dtype, case):
     check(got, ref, dtype, "conv " + case)
 
 
-@pytest.mark.parametrize("N,C,Co,hw", [(2, 64, 320, 96), (4, 64, 320, 128), (1, 64, 640, 40), (4, 128, 320, 96)])  # last: 576 tiles -> tail split
+_TILE_CONFIG_ROUTES = {
+    (2, 64, 320, 96): dict(kernel="glds", config=4, splits=1),                                   # 288 tiles of 128 rows -> D
+    (4, 64, 320, 128): dict(kernel="conv_pp", config=1, rowhalo=2, splits=1),                    # 1024 tiles -> A's place: 512 tiles of 256 pixels on conv_pp
+    (1, 64, 640, 40): dict(kernel="glds", config=3, splits=1),                                   # 26 tiles of 128 rows -> C
+    (4, 128, 320, 96): dict(kernel="rowhalo", config=1, rowhalo=1, halo_lin=1, splits=1, tail_splits=4, reduce="plain")}  # 576 tiles -> tail split
+
+
+@pytest.mark.parametrize("N,C,Co,hw", list(_TILE_CONFIG_ROUTES))
 def test_conv2d_tile_configs(N, C, Co, hw):
-    """bf16 3x3 convs sized to land on configurations D (288 tiles of 128 rows), A (1024 blocks) and C (26 tiles of 128 rows)."""
+    """bf16 3x3 convs sized to land on configurations D (288 tiles of 128 rows) and C (26 tiles of 128 rows) of the generic implicit GEMM,
+    and on the two kernels that stand in configuration A's place for 3x3 convs: the 256-pixel-tile kernel (1024 tiles of 128 rows) and the
+    row-halo kernel with a K-split tail (576 tiles)."""
     from cremage_amd import ops
     x, w, b = rnd(N, C, hw, hw, seed=30), rnd(Co, C, 3, 3, seed=31, scale=(C * 9) ** -0.5), rnd(Co, seed=32)
     res = rnd(N, Co, hw, hw, seed=33)
     ref = conv_ref(x, w, b, BF) + q(res, BF)
     got = ops.conv2d(nhwc(x, BF), w.to(_dev()), b.to(_dev()), residual=nhwc(res, BF))
+    assert_route(f"conv cfg {N}x{C}x{hw}x{hw}->{Co}", **_TILE_CONFIG_ROUTES[(N, C, Co, hw)])
     check(got, ref, BF, f"conv cfg {N}x{C}x{hw}x{hw}->{Co}")
 
 
@@ -415,25 +445,48 @@ def test_split_planes_path(C, Co, ks):
         ops.conv2d(hi, w.to(_dev()), bias.to(_dev()), x_lo=lo.float())
 
 
-@pytest.mark.parametrize("N,C1,C2,H,W,Co", [
-    (2, 64, 0, 16, 16, 64),       # one chunk, tiles of 8 image rows
-    (1, 128, 64, 24, 32, 160),    # virtual concat, H != W, 160-wide tiles
-    (3, 64, 0, 5, 16, 96),        # M = 240: tile tail, tiles straddling images
-    (2, 72, 56, 16, 32, 64),      # concat boundary inside a 64-channel chunk
-    (1, 1280, 0, 16, 16, 128),    # long K: split-K slices in (chunk, kernel row) groups
-    (1, 64, 0, 4, 128, 64),       # one image row per tile
-    (2, 320, 0, 64, 64, 320),     # production shape (SD1.5 64x64 level)
-    (8, 640, 0, 32, 32, 640),     # production shape: 256 tiles -> two K slices
-    (2, 64, 0, 9, 7, 64),         # linear-pixel row buffer: width 7, M = 126 (one partial tile)
-    (2, 128, 64, 24, 40, 96),     # linear: ragged latent, concat
-    (1, 320, 0, 96, 96, 320),     # linear: 768x768 image level (C4), 256-row tiles
-    (3, 64, 0, 8, 8, 64),         # linear: 8x8 level, tiles straddling images
-    (1, 64, 0, 2, 200, 64),       # linear: rows longer than a tile
-    (4, 128, 0, 96, 96, 320),     # 576 tiles = 512 + 64: tail split (second launch cut along K in row groups) on the linear buffer
-])
+_GENERIC_C = dict(kernel="glds", config=3, splits=1, rowhalo=0)  # fewer than 192 tiles and a K too short to cut: the generic implicit GEMM
+
+
+def _halo(splits, lin=0, **kw):
+    return dict(dict(kernel="rowhalo", config=1, rowhalo=1, halo_lin=lin, splits=splits, reduce="plain" if splits > 1 else "none"), **kw)
+
+
+_ROWHALO_ROUTES = {
+    # The row-halo kernel exists in configuration A only, which a 3x3 conv reaches with at least 384 tiles of 128 rows or with a K worth
+    # cutting (>= 24 k-tiles: Cin >= 192).  The small 64-channel shapes below were written for it but run on configuration C of the
+    # generic implicit GEMM; they stay as they are (same geometry on the other kernel) and each has a 192-channel twin that does reach
+    # the row-halo kernel.
+    (2, 64, 0, 16, 16, 64): _GENERIC_C,       # one chunk
+    (2, 192, 0, 16, 16, 64): _halo(3),        # ... row-halo: tiles of 8 image rows
+    (1, 128, 64, 24, 32, 160): _halo(3),      # virtual concat, H != W, 160-wide tiles
+    (3, 64, 0, 5, 16, 96): _GENERIC_C,        # M = 240: tile tail
+    (3, 192, 0, 5, 16, 96): _halo(3),         # ... row-halo: tile tail, tiles straddling images
+    (2, 72, 56, 16, 32, 64): _GENERIC_C,      # concat boundary inside a 64-channel chunk
+    (2, 136, 56, 16, 32, 64): _halo(3),       # ... row-halo: concat boundary inside the third chunk
+    (1, 1280, 0, 16, 16, 128): _halo(16),     # long K: split-K slices in (chunk, kernel row) groups
+    (1, 64, 0, 4, 128, 64): _GENERIC_C,       # W = 128
+    (1, 192, 0, 4, 128, 64): _halo(3),        # ... row-halo: one image row per tile
+    (2, 320, 0, 64, 64, 320): _GENERIC_C,     # SD1.5 64x64 level at batch 2: 128 tiles, 45 k-tiles -> C, unsplit
+    (8, 640, 0, 32, 32, 640): dict(kernel="conv_pp", config=1, rowhalo=2, splits=2, reduce="plain"),  # production shape: 128 tiles of 256 pixels x two K slices
+    (2, 64, 0, 9, 7, 64): _GENERIC_C,         # width 7, M = 126 (one partial tile)
+    (2, 192, 0, 9, 7, 64): _halo(3, 1),       # ... row-halo, linear-pixel row buffer
+    (2, 128, 64, 24, 40, 96): _halo(3, 1),    # linear: ragged latent, concat
+    (1, 320, 0, 96, 96, 320): _GENERIC_C,     # 768x768 image level at batch 1: 144 tiles -> C (test_conv_256_pixel_tile_shapes has the linear buffer on 256-row tiles)
+    (3, 64, 0, 8, 8, 64): _GENERIC_C,         # 8x8 level
+    (3, 192, 0, 8, 8, 64): _halo(3, 1),       # ... row-halo, linear: tiles straddling images
+    (1, 64, 0, 2, 200, 64): _GENERIC_C,       # W = 200
+    (1, 192, 0, 2, 200, 64): _halo(3, 1),     # ... row-halo, linear: rows longer than a tile
+    (4, 128, 0, 96, 96, 320): _halo(1, 1, tail_splits=4, reduce="plain"),  # 576 tiles = 512 + 64: tail split (second launch cut along K in row groups) on the linear buffer
+    (1, 64, 0, 777, 16, 640): _halo(1, tail_splits=0),  # 98 x 4 = 392 tiles, 9 k-tiles: unsplit grid with a ragged last tile (M = 97 * 128 + 16)
+}
+
+
+@pytest.mark.parametrize("N,C1,C2,H,W,Co", list(_ROWHALO_ROUTES))
 def test_conv_rowhalo_shapes(N, C1, C2, H, W, Co):
-    """3x3 / stride 1 / pad 1 convs whose width divides 128 run on conv3_rowhalo_kernel (one halo'd row buffer per kernel row
-    instead of one activation tile per tap): image borders, tile tails, concat inputs, split-K and every fused epilogue term."""
+    """3x3 / stride 1 / pad 1 convs on conv3_rowhalo_kernel (one halo'd row buffer per kernel row instead of one activation tile per
+    tap) - and, for the shapes too small to reach it, on the generic implicit GEMM: image borders, tile tails, concat inputs, split-K
+    and every fused epilogue term.  Each case asserts the kernel it ran."""
     from cremage_amd import ops
     C = C1 + C2
     x = rnd(N, C1, H, W, seed=80)
@@ -444,6 +497,7 @@ def test_conv_rowhalo_shapes(N, C1, C2, H, W, Co):
         ref = conv_ref(x, w, b, BF, x2=x2, **kw)
         got = ops.conv2d(nhwc(x, BF), w.to(_dev()), b.to(_dev()), x2=nhwc(x2, BF) if C2 else None,
                          cvec=kw["cvec"].to(_dev()) if "cvec" in kw else None, residual=nhwc(kw["res"], BF) if "res" in kw else None)
+        assert_route(f"rowhalo conv {N}x{C1}+{C2}x{H}x{W}->{Co} {sorted(kw)}", **_ROWHALO_ROUTES[(N, C1, C2, H, W, Co)])
         check(got, ref, BF, f"rowhalo conv {N}x{C1}+{C2}x{H}x{W}->{Co} {sorted(kw)}")
 
 
@@ -454,7 +508,8 @@ def test_conv_rowhalo_shapes(N, C1, C2, H, W, Co):
     (8, 1280, 0, 16, 16, 1280, False),  # 64 tiles x 4 K slices, 16 whole image rows per tile
     (8, 1280, 0, 8, 8, 1280, False),    # linear-pixel row buffer (8x8 level), 16 K slices
     (8, 640, 0, 32, 32, 640, True),     # nearest-2x upsample folded into the gather, 64x64 output
-    (8, 192, 64, 64, 64, 128, False),   # 128-wide tiles (WNT = 4), concat
+    (8, 192, 64, 64, 64, 128, False),   # 128 outputs = one n-tile: 128 blocks of 256 pixels fill half a round, below the 85 % rule -> 64-row tiles (D) of the generic kernel
+    (14, 64, 64, 64, 64, 128, False),   # ... 224 blocks do: conv_pp with 128-wide tiles (WNT = 4), concat
     (2, 128, 0, 128, 128, 320, False),  # W = 128 divides the tile: two image rows per tile
     (1, 128, 0, 64, 512, 320, False),   # W = 512 > tile: one 256-pixel row SEGMENT per tile
 ])
@@ -462,6 +517,10 @@ def test_conv_256_pixel_tile_shapes(N, C1, C2, H, W, Co, up):
     """3x3 convs whose grid fills rounds of 256-pixel tiles run on conv3_pp_kernel (conv_pp.hip: 4-slot weight ring, counted vmcnt,
     the two waves of a SIMD half a k-tile apart): every buffer geometry, split-K, concat, upsample and epilogue term."""
     from cremage_amd import ops
+    splits = {(8, 640, 32, False): 2, (8, 1280, 16, False): 4, (8, 1280, 8, False): 16}.get((N, C1, H, up), 1)
+    route = dict(kernel="conv_pp", config=1, rowhalo=2, wnt=4 if Co == 128 else 5, splits=splits, halo_lin=1 if W == 8 else 0, reduce="plain" if splits > 1 else "none")
+    if (N, Co) == (8, 128):
+        route = dict(kernel="glds", config=4, wnt=4, splits=1, rowhalo=0)
     C = C1 + C2
     x = rnd(N, C1, H, W, seed=180)
     x2 = rnd(N, C2, H, W, seed=181) if C2 else None
@@ -472,6 +531,7 @@ def test_conv_256_pixel_tile_shapes(N, C1, C2, H, W, Co, up):
         ref = conv_ref(x, w, b, BF, x2=x2, up=up, **kw)
         got = ops.conv2d(nhwc(x, BF), w.to(_dev()), b.to(_dev()), x2=nhwc(x2, BF) if C2 else None, upsample2x=up,
                          cvec=kw["cvec"].to(_dev()) if "cvec" in kw else None, residual=nhwc(kw["res"], BF) if "res" in kw else None)
+        assert_route(f"ring conv {N}x{C1}+{C2}x{H}x{W}->{Co} up={up} {sorted(kw)}", **route)
         check(got, ref, BF, f"ring conv {N}x{C1}+{C2}x{H}x{W}->{Co} up={up} {sorted(kw)}")
 
 
@@ -613,6 +673,7 @@ def test_conv_planes_gn_stats(N, C, H, W, Co, with_res):
     g, be = (1 + 0.1 * rnd(Co, seed=194)).to(_dev()), (0.1 * rnd(Co, seed=195)).to(_dev())
     hi, lo = ops.split_bf16(nhwc(x, torch.float32))
     y = ops.conv2d(hi, w.to(_dev()), b.to(_dev()), x_lo=lo, residual=nhwc(res, torch.float32) if with_res else None, gn_stats=True)
+    assert_route(f"planes conv + statistics {N}x{C}x{H}x{W}->{Co}", kernel="planes", rowhalo=1, splits=1, reduce="none", mx=0, gn_stats_rows=32)
     st = getattr(y, "_crg_gn", None)
     assert st is not None, "the planes conv did not attach its statistics"
     rows = y.permute(0, 2, 3, 1).reshape(-1, Co).double()                      # [M][Co] in the kernel's row order
@@ -729,22 +790,38 @@ def _stats_ref(y, hw, rows=32):
     return torch.stack([t.sum(1), (t * t).sum(1)])
 
 
-@pytest.mark.parametrize("case", ["conv_unsplit", "conv_splitk", "conv_pairless_tail", "linear_cfgA", "linear_cfgC", "linear_cfgD", "conv_stride2"])
+_GN_STATS_ROUTES = {
+    "conv_unsplit": dict(kernel="conv_pp", rowhalo=2, splits=1, pair=1, reduce="none", gn_stats_rows=256),       # tile partials
+    "conv_splitk": dict(kernel="conv_pp", rowhalo=2, splits=8, reduce="stats", gn_stats_rows=32),
+    # 576 tiles, but 9 k-tiles are too few for a K-split tail (and the paired epilogue is in use): the row-halo kernel on a grid whose
+    # second round is 1/8 full.  The id keeps its old name.
+    "conv_pairless_tail": dict(kernel="rowhalo", rowhalo=1, splits=1, tail_splits=0, pair=1, reduce="none", gn_stats_rows=32),
+    "conv_tail_split": dict(kernel="rowhalo", rowhalo=1, splits=1, tail_splits=4, pair=1, reduce="stats", gn_stats_rows=32),  # 18 k-tiles: the tail's reduce writes its rows' statistics
+    "conv_stride2": dict(kernel="glds", config=3, splits=1, pair=1, reduce="none", gn_stats_rows=32),
+    "linear_cfgA": dict(kernel="glds", config=1, splits=1, pair=1, reduce="none", gn_stats_rows=32),
+    "linear_cfgC": dict(kernel="glds", config=3, splits=1, pair=1, reduce="none", gn_stats_rows=32),
+    "linear_cfgD": dict(kernel="glds", config=4, splits=1, pair=1, reduce="none", gn_stats_rows=32),
+}
+
+
+@pytest.mark.parametrize("case", ["conv_unsplit", "conv_splitk", "conv_pairless_tail", "conv_tail_split", "linear_cfgA", "linear_cfgC", "linear_cfgD", "conv_stride2"])
 def test_gn_stats_side_channel(case):
     """The GroupNorm statistics a conv / linear writes next to its output (crg_*_args.gn_stats) equal the sums over its STORED bf16
-    output, on every code path that writes them: the paired epilogue (three tile configurations, the 256-pixel ring conv), the
-    split-K reduce kernel, a stride-2 conv; and group_norm() on such a tensor equals group_norm() with its own statistics pass."""
+    output, on every code path that writes them: the paired epilogue (three tile configurations of the GEMM, the row-halo conv, the
+    256-pixel ring conv with tile partials), the split-K reduce kernel (whole problem, and the rows of a K-split tail), a stride-2 conv;
+    and group_norm() on such a tensor equals group_norm() with its own statistics pass."""
     from cremage_amd import ops
     dev = _dev()
     if case.startswith("conv"):
         N, Cin, Cout, hw, stride = {"conv_unsplit": (8, 64, 320, 64, 1), "conv_splitk": (2, 640, 640, 32, 1), "conv_pairless_tail": (9, 64, 320, 64, 1),
-                                    "conv_stride2": (4, 128, 320, 64, 2)}[case]
+                                    "conv_tail_split": (9, 128, 320, 64, 1), "conv_stride2": (4, 128, 320, 64, 2)}[case]
         x = rnd(N, Cin, hw, hw, seed=200)
         w, b = rnd(Cout, Cin, 3, 3, seed=201, scale=(9 * Cin) ** -0.5), rnd(Cout, seed=202)
         cv = rnd(N, Cout, seed=203).to(dev)
         ho = hw // stride
         r = rnd(N, Cout, ho, ho, seed=204)
         y = ops.conv2d(nhwc(x, BF), w.to(dev), b.to(dev), stride=stride, padding=1, cvec=cv, residual=nhwc(r, BF), gn_stats=True)
+        assert_route(case, **_GN_STATS_ROUTES[case])
         ref = F.conv2d(q(x, BF), q(w, BF), b, stride=stride, padding=1) + cv.cpu()[:, :, None, None] + q(r, BF)
         C = Cout
     else:
@@ -752,6 +829,7 @@ def test_gn_stats_side_channel(case):
         x, w, b, r = rnd(M, K, seed=210), rnd(Nn, K, seed=211, scale=K ** -0.5), rnd(Nn, seed=212), rnd(M, Nn, seed=213)
         side = int(hw ** 0.5)
         t = ops.linear(x.to(dev).to(BF).view(M // hw, hw, K), w.to(dev), b.to(dev), residual=r.to(dev).to(BF).view(M // hw, hw, Nn), gn_hw=hw)
+        assert_route(case, **_GN_STATS_ROUTES[case])
         y = ops.image_of_stats(t, side, side)
         ref = (F.linear(q(x, BF), q(w, BF), b) + q(r, BF)).view(M // hw, side, side, Nn).permute(0, 3, 1, 2)
         C = Nn
