@@ -44,6 +44,7 @@ class GemmArgs(C.Structure):
         ("vt", c_void_p), ("vt_n0", c_int), ("vt_tokens", c_int), ("vt_ld", c_int64),
         ("row_stats", c_void_p), ("row_stats_parts", c_int),
         ("ln_stats", c_void_p), ("ln_parts", c_int), ("ln_colsum", c_void_p), ("ln_eps", c_float),
+        ("rows_per_sample", c_int),
     ]
 
 
@@ -208,6 +209,8 @@ SIGNATURES = {
     "crg_ctx_destroy": (None, [c_void_p]),
     "crg_last_error": (C.c_char_p, [c_void_p]),
     "crg_ctx_reserve": (c_int, [c_void_p, c_size_t]),
+    "crg_ctx_set_invariant": (c_int, [c_void_p, c_int]),
+    "crg_ctx_get_invariant": (c_int, [c_void_p]),
     "crg_kernel_name": (C.c_char_p, [c_int]),
     "crg_profile_begin": (c_int, [c_void_p]),
     "crg_profile_end": (c_int, [c_void_p, c_void_p, C.POINTER(Profile)]),
@@ -300,6 +303,45 @@ _ctxs = {}
 _lane = 0
 
 
+# ---- batch-invariant mode (crg_ctx_set_invariant; cremage_amd.set_batch_invariant is the public switch) ----
+def parse_invariant(value, what="set_batch_invariant"):
+    """tune_samples as the library takes it: None / 0 -> 0 (off), a positive integer -> itself.  A bool, a negative number or a
+    non-integer is a ValueError."""
+    if value is None:
+        return 0
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f"{what}: tune_samples must be None or a non-negative integer, got {value!r}")
+    if value < 0 or value >= 1 << 31:
+        raise ValueError(f"{what}: tune_samples must be None or a non-negative integer below 2^31, got {value!r}")
+    return int(value)
+
+
+def parse_invariant_env(text):
+    """CRG_BATCH_INVARIANT=<n>: empty / unset -> 0 (off), a decimal non-negative integer -> itself; anything else is a ValueError."""
+    if text is None or text.strip() == "":
+        return 0
+    t = text.strip()
+    if not t.isdigit():
+        raise ValueError(f"CRG_BATCH_INVARIANT={text!r}: a non-negative integer expected (0 = off)")
+    return parse_invariant(int(t), "CRG_BATCH_INVARIANT")
+
+
+_invariant = parse_invariant_env(os.environ.get("CRG_BATCH_INVARIANT"))
+
+
+def invariant() -> int:
+    """tune_samples of the batch-invariant mode, 0 = off."""
+    return _invariant
+
+
+def set_invariant(tune_samples: int) -> None:
+    """Set the mode on every live context and remember it for those created later (host bookkeeping, no launch)."""
+    global _invariant
+    _invariant = parse_invariant(tune_samples)
+    for h in _ctxs.values():
+        check(load().crg_ctx_set_invariant(h, _invariant), h, "crg_ctx_set_invariant")
+
+
 def set_lane(i: int) -> int:
     """Select which of the device's contexts the following crg_* calls use.  A context owns scratch (split-K slabs, GroupNorm
     partials) and is not re-entrant, so work that runs CONCURRENTLY on several HIP streams needs one context per stream
@@ -320,6 +362,8 @@ def ctx(device_index: int):
         if rc != 0:
             raise CrgError(f"crg_ctx_create(device={device_index}) failed with {rc}: no usable HIP device")
         h = out
+        if _invariant:
+            check(lib.crg_ctx_set_invariant(h, _invariant), h, "crg_ctx_set_invariant")
         _ctxs[key] = h
     return h
 

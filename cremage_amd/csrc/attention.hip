@@ -1332,7 +1332,8 @@ static int attention_entry(crg_ctx* ctx, void* stream, const void* q, int64_t ld
   // staging is the faster one, 12.6 vs 13.5 us).  These launches are bound by their 80-byte-per-head Q / O row slices (32 cache
   // lines per wave-instruction), not by block count: see DESIGN 4.
   const int nqg_ = (Nq + 127) / 128;
-  if (use_ctx && Nk <= 128 && (long)nqg_ * B * H >= 2048) {
+  // (batch-invariant mode: the block count of tune_samples samples, crg_heur_samples - the two kernels sum the keys in different orders)
+  if (use_ctx && Nk <= 128 && (long)nqg_ * crg_heur_samples(ctx, B) * H >= 2048) {
     switch (ks) {
       case 1: return launch_attn_ctx<1, 1>(ctx, st, p, vrm);
       case 2: return launch_attn_ctx<2, 1>(ctx, st, p, vrm);

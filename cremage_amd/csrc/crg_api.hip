@@ -86,6 +86,14 @@ extern "C" int crg_last_route(crg_ctx* ctx, crg_route* out) {
   return 0;
 }
 
+extern "C" int crg_ctx_set_invariant(crg_ctx* ctx, int tune_samples) {
+  if (!ctx) return -22;
+  CRG_REQUIRE(ctx, tune_samples >= 0, "ctx_set_invariant: tune_samples = %d (0 = off, >= 1 = on)", tune_samples);
+  ctx->invariant = tune_samples;
+  return 0;
+}
+extern "C" int crg_ctx_get_invariant(crg_ctx* ctx) { return ctx ? ctx->invariant : -22; }
+
 extern "C" int crg_ctx_reserve(crg_ctx* ctx, size_t bytes) {
   if (!ctx) return -22;
   return crg_scratch(ctx, bytes) ? 0 : crg_fail(ctx, -12, "cannot reserve %zu bytes of scratch", bytes);

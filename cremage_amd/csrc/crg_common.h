@@ -56,7 +56,13 @@ struct crg_ctx {
   bool profiling = false;
   std::vector<crg_prof_rec> recs;
   std::vector<hipEvent_t> event_pool;
+  // batch-invariant mode (crg_ctx_set_invariant): 0 = off, else tune_samples - the sample count every size heuristic
+  // reads in place of the call's own, so that what is computed for one sample does not depend on what shares the launch
+  int invariant = 0;
 };
+
+// the sample count a size heuristic reads: the call's own, or tune_samples under the batch-invariant mode
+inline long crg_heur_samples(const crg_ctx* ctx, long actual) { return ctx->invariant > 0 ? ctx->invariant : actual; }
 
 int crg_fail(crg_ctx* ctx, int code, const char* fmt, ...);
 // scratch of at least `bytes` (grows with hipMalloc when too small: NOT capture-safe, so callers

@@ -1549,10 +1549,11 @@ int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, int batch) {
 // Split-K factor: small-M problems (8x8 / 16x16 UNet levels, token GEMMs with few rows) launch far fewer
 // than 2 blocks per CU and stream long K; cut K so that ~512 blocks are in flight, keeping >= 8 k-tiles
 // per slice.  Costs one fp32 slab round trip + one extra launch, so only when the tile count is low.
-inline int choose_splits(const GemmP& p, int tiles, int batch) {
+// `blocks`: tiles x batch as the size heuristics count them (heur_blocks: the call's own, or those of tune_samples samples under the
+// batch-invariant mode)
+inline int choose_splits(const GemmP& p, long blocks) {
   if (p.epi == CRG_EPI_GEGLU || (p.N & 3) || p.ln_stat) return 1;  // (the LayerNorm correction is per whole row sum: no K slices)
   const int nk = (p.K + BK - 1) / BK;
-  const long blocks = (long)tiles * batch;
   // 256..511 blocks leave one block (4 waves) on most CUs, which hides neither the barrier nor the DMA latency: cut K in
   // two when it is long enough to amortise the slab pass (measured: 8x32x32 640->640 conv 112 -> 89 us, 1280->640 203 -> 137 us;
   // K = 2560 GEMMs lose 5 %, hence the nk bound)
@@ -1583,8 +1584,30 @@ inline int choose_splits(const GemmP& p, int tiles, int batch) {
   return s < 2 ? 1 : s;
 }
 
-struct Work {  // algorithmic work of one call (profiler) and operand footprints (XCD partition)
+// What the size heuristics of one call read (host only; built by heur_of for every call, so no entry point can inherit another call's):
+// the call's own rows and batch with the batch-invariant mode off; tune_samples samples of the per-sample problem with it on (rps =
+// rows per sample then, else 0).
+struct Heur {
+  long M;
+  int batch, rps;
+};
+
+inline Heur heur_of(const crg_ctx* ctx, long M, int batch, int rps, bool samples_along_batch) {
+  if (ctx->invariant <= 0) return Heur{M, batch, 0};
+  if (samples_along_batch) return Heur{M, ctx->invariant, 0};
+  return Heur{(long)ctx->invariant * rps, batch, rps};
+}
+
+// Blocks of `rows`-row tiles the size heuristics count: p.tiles_n x ceil(M / rows) x batch of the call itself - or, under the
+// batch-invariant mode, of tune_samples samples of the per-sample problem (Heur), so that no decision taken from it depends on how
+// many samples share the launch.  The launch itself always covers the real p.M.
+inline long heur_blocks(const Heur& h, const GemmP& p, int rows) {
+  return (long)p.tiles_n * ((h.M + rows - 1) / rows) * h.batch;
+}
+
+struct Work {  // algorithmic work of one call (profiler), operand footprints (XCD partition) and the sizes its heuristics read
   double flops, bytes, a_bytes, w_bytes;
+  Heur heur;
 };
 
 // (xg_m, xg_n, xg_s): see block_to_tile.  Minimise fabric traffic xg_n*|A| + xg_m*|W| over the feasible factorizations of 8.
@@ -1726,14 +1749,22 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   // split-K first, on 128-row tiles: a long K is the cheapest source of blocks.  Only problems that stay below ~1 block per
   // CU after that (short K) change the tile / wave configuration.
   p.tiles_m = (p.M + 127) / 128;
-  p.splits = choose_splits(p, p.tiles_n * p.tiles_m, batch);
+  const bool inv = ctx->invariant > 0;  // batch-invariant mode: every size below is that of tune_samples samples (heur_blocks)
+  p.splits = choose_splits(p, heur_blocks(wk.heur, p, 128));
   if constexpr (GLDS && !CONV && sizeof(YT) == 2) {
     // persistent 256-row tiles (gemm_ring.hip) where every CU gets at least (almost) one: more FLOP per staged byte, no per-tile prologue
-    if (ring_gemm_ok(p, batch, ctx->n_cu)) return launch_gemm_ring(ctx, st, p, wk.flops, wk.bytes);
+    // (batch-invariant mode, a_is_weight: `batch` is the sample count, which ring_gemm_ok reads - dev knob CRG_GEMM_RING=2 only, since
+    // the default rule takes GEGLU GEMMs alone - so those calls stay on the kernel below whatever their batch)
+    if (!(inv && p.a_is_weight) && ring_gemm_ok(p, batch, ctx->n_cu, wk.heur.M)) {
+      if (ring_gemm_fits(p)) return launch_gemm_ring(ctx, st, p, wk.flops, wk.bytes);
+      // (mode off: the two-blocks-per-CU kernel takes what the descriptors cannot address.  Under the mode that would be a route picked by
+      // the size of the call)
+      if (inv) return crg_fail(ctx, -22, "gemm: batch-invariant mode routes this problem to the persistent 256-row kernel, whose 32-bit buffer descriptors cannot address M=%d rows: split the call", p.M);
+    }
   }
   int cfg = 1;
   if (GLDS && p.splits == 1) {
-    const long blocks = (long)p.tiles_m * p.tiles_n * batch;
+    const long blocks = heur_blocks(wk.heur, p, 128);
     static const int d_max = getenv("CRG_GEMM_D_MAX") ? atoi(getenv("CRG_GEMM_D_MAX")) : 384;      // dev knob: 64-row tiles below this many 128-row tiles (plain epilogues)
     static const int d_max_g = getenv("CRG_GEMM_D_MAXG") ? atoi(getenv("CRG_GEMM_D_MAXG")) : 384;  // ... GEGLU epilogues
     static const int d_max_c1 = getenv("CRG_CONV1_D_MAX") ? atoi(getenv("CRG_CONV1_D_MAX")) : 384;   // ... 1x1 convs (virtual-concat skip convs)
@@ -1745,17 +1776,18 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   if (p.up == 2) cfg = 1;  // the sub-pixel upsample form exists on the row-halo kernel (configuration A's place) only
   if (cfg == 3 || cfg == 4) {
     p.tiles_m = (p.M + 63) / 64;
-    p.splits = force ? choose_splits(p, p.tiles_n * p.tiles_m, batch) : 1;
+    p.splits = force ? choose_splits(p, heur_blocks(wk.heur, p, 64)) : 1;
   }
   if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     // row-halo conv on 256-row tiles (one 8-wave block per CU): same K slices, half the m-tiles
     static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 2;  // dev knob: 0 plain implicit GEMM, 1 128-row tiles only
     const int ngroups = (p.K / BK) / (p.up == 2 ? 2 : 3);
     const int Wg = p.up == 2 ? p.W : p.Wo;  // (sub-pixel form: source-grid geometry, tiles must not straddle a parity)
-    if (knob == 2 && cfg == 1 && p.rowhalo && batch == 1 && p.splits <= ngroups && p.M % 256 == 0 &&
+    // (batch-invariant mode: whole tiles per SAMPLE, so that the form does not come and go with the parity of the sample count)
+    if (knob == 2 && cfg == 1 && p.rowhalo && batch == 1 && p.splits <= ngroups && (inv ? wk.heur.rps % 256 == 0 : p.M % 256 == 0) &&
         (p.halo_lin || (Wg <= 256 ? 256 % Wg == 0 : Wg % 256 == 0)) && (p.up != 2 || (p.H * p.W) % 256 == 0)) {
       // one block per CU: only when the grid fills its rounds of 256 blocks (a 288-block grid would run a second round 1/8 full)
-      const long blocks2 = (long)(p.M / 256) * p.tiles_n * p.splits;
+      const long blocks2 = heur_blocks(wk.heur, p, 256) * p.splits;
       const long rounds = (blocks2 + 255) / 256;
       if (blocks2 * 100 >= rounds * 256 * 85) {
         p.rowhalo = 2;
@@ -1766,7 +1798,11 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
   p.ring = 0;
   if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
     // the staggered-wave kernel (conv_pp.hip) for the 256-row configuration, where its buffer descriptors can address the operands
-    if (p.rowhalo == 2 && p.up != 2 && p.a_bytes && p.w_bytes && (p.C2 == 0 || p.x2_bytes) && (long)p.M / (p.Ho * p.Wo) * p.H * p.W < (1 << 24)) p.ring = 1;
+    if (p.rowhalo == 2 && p.up != 2 && p.w_bytes) {
+      const bool fits = p.a_bytes && (p.C2 == 0 || p.x2_bytes) && (long)p.M / (p.Ho * p.Wo) * p.H * p.W < (1 << 24);  // the only clause that reads the sample count
+      if (fits) p.ring = 1;
+      else if (inv) return crg_fail(ctx, -22, "conv2d: batch-invariant mode routes this conv to the staggered 256-pixel-tile kernel, whose buffer descriptors cannot address %d samples of %d x %d: split the call", p.M / (p.Ho * p.Wo), p.H, p.W);
+    }
   }
   if (p.splits > 1) {
     const size_t bytes = (size_t)batch * p.splits * p.M * p.N * sizeof(float);
@@ -1786,7 +1822,8 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     const int T = p.tile_count, nk = (p.K + BK - 1) / BK;
     const int r = T % 512, T1 = T - r;
     // (not with a transposed column range: the K-split tail would have to emit V^T from the reduce pass - ADVICE r3)
-    if (cfg == 1 && p.rowhalo != 2 && p.splits == 1 && batch == 1 && T1 >= 512 && r > 0 && r <= 224 && nk >= 16 && r % p.tiles_n == 0 &&
+    // (off under the batch-invariant mode: which rows fall into the tail depends on the sample's position in the call)
+    if (!inv && cfg == 1 && p.rowhalo != 2 && p.splits == 1 && batch == 1 && T1 >= 512 && r > 0 && r <= 224 && nk >= 16 && r % p.tiles_n == 0 &&
         p.epi != CRG_EPI_GEGLU && !(p.N & 3) && !p.vt && !p.rstat && !p.ln_stat) {
       int s2 = 512 / r;
       if (s2 > nk / 4) s2 = nk / 4;
@@ -1797,7 +1834,7 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
         if (!slab) return crg_fail(ctx, -12, "gemm: out of scratch for the tail slab");
         p.xg_s = 0;  // partial ranges use the contiguous-run order
         p.tile_count = T1;
-        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * T1 / T, wk.bytes * T1 / T, 0, 0});
+        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * T1 / T, wk.bytes * T1 / T, 0, 0, wk.heur});
         if (rc) return rc;
         p.tile_base = T1;
         p.tile_count = r;
@@ -1805,7 +1842,7 @@ int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
         p.slab = slab;
         p.slab_row0 = row0;
         const int pair1 = ctx->route.pair;
-        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * r / T, wk.bytes * r / T, 0, 0});
+        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * r / T, wk.bytes * r / T, 0, 0, wk.heur});
         if (rc) return rc;
         ctx->route.splits = 1;  // the record describes the main launch; of the tail it keeps the K cut
         ctx->route.pair = pair1;
@@ -1838,7 +1875,7 @@ int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
     return crg_fail(ctx, -22, "gemm/conv: GroupNorm statistics need an unbatched problem with N %% 4 == 0 and M %% 32 == 0");
   p.tiles_n = (p.N + BN - 1) / BN;
   p.tiles_m = (p.M + 127) / 128;
-  p.splits = p.gstat ? 1 : choose_splits(p, p.tiles_n * p.tiles_m, batch);  // the statistics come out of the epilogue: no K split
+  p.splits = p.gstat ? 1 : choose_splits(p, heur_blocks(wk.heur, p, 128));  // the statistics come out of the epilogue: no K split
   if (p.splits > 1) {
     p.slab = (float*)crg_scratch(ctx, (size_t)batch * p.splits * p.M * p.N * sizeof(float));
     if (!p.slab) return crg_fail(ctx, -12, "gemm: out of scratch for %d split-K slabs", p.splits);
@@ -1991,11 +2028,17 @@ extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
                 "gemm: ln_stats needs ln_colsum, an even number of 2..16 partials per row and 16-byte aligned pointers");
     p.ln_stat = a->ln_stats; p.ln_parts = a->ln_parts; p.ln_s = a->ln_colsum; p.ln_eps = a->ln_eps;
   }
+  // what the size heuristics read (heur_blocks): the call itself, or - batch-invariant mode - tune_samples samples of the per-sample problem
+  // (a_is_weight, transposed outputs: the rows are the weight's, the samples lie along `batch`)
+  const int rps = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
+  if (ctx->invariant > 0 && !a->a_is_weight)
+    CRG_REQUIRE(ctx, a->M % rps == 0, "gemm: batch-invariant mode: M=%d is not a whole number of samples of rows_per_sample=%d rows", a->M, rps);
+  const Heur heur = heur_of(ctx, a->M, a->batch, rps, a->a_is_weight != 0);
   const double flops = 2.0 * a->M * (double)a->N * a->K * a->batch;
   const double bytes = ((double)a->M * a->K * crg_dtype_size(a->a_dtype) + (double)a->N * a->K * 2 +
                         (double)a->M * a->N * crg_dtype_size(a->y_dtype) * (a->residual ? 2 : 1)) * a->batch;
   return dispatch<false>(ctx, (hipStream_t)stream, p, a->batch, a->a_dtype, a->y_dtype, a->prec,
-                         Work{flops, bytes, (double)a->M * a->K * crg_dtype_size(a->a_dtype), (double)a->N * a->K * 2});
+                         Work{flops, bytes, (double)a->M * a->K * crg_dtype_size(a->a_dtype), (double)a->N * a->K * 2, heur});
 }
 
 extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
@@ -2087,8 +2130,9 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   const double bytes = (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype) + wbytes +
                        (double)p.M * p.N * crg_dtype_size(a->y_dtype) * (a->residual ? 2 : 1);
   ctx->gn_fused = false;
+  const Heur heur = heur_of(ctx, p.M, 1, a->Ho * a->Wo, false);  // batch-invariant mode: tune_samples samples of Ho x Wo rows
   const int rc = dispatch<true>(ctx, (hipStream_t)stream, p, 1, a->x_dtype, a->y_dtype, a->prec,
-                                Work{flops, bytes, (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype), wbytes});
+                                Work{flops, bytes, (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype), wbytes, heur});
   if (a->gn_stats_rows) *a->gn_stats_rows = p.gstat_rows;
   if (rc || !a->gn_y || ctx->gn_fused) return rc;
   // not split along K (or a shape the fused kernel does not take): the GroupNorm runs as its own launch(es) on the finished y

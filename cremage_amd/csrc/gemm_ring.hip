@@ -470,7 +470,9 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
 //                                       32) then cost more issue time than the larger tile saves
 // so it is routed for GEGLU GEMMs with at least three 256-row tiles per CU.  CRG_GEMM_RING: 0 = never, 1 (default) = that rule,
 // 2 = plain epilogues as well (from CRG_GEMM_RING_MIN percent of a tile per CU, default 300).
-bool ring_gemm_ok(const GemmP& p, int batch, int n_cu) {
+// `heur_M`: the rows the tile count is taken from (the call's own, or those of tune_samples samples under the batch-invariant mode: the
+// kernel is then also launched on fewer tiles than CUs - grid = tile count, one tile per block, every block non-empty).
+bool ring_gemm_ok(const GemmP& p, int batch, int n_cu, long heur_M) {
   static const int on = getenv("CRG_GEMM_RING") ? atoi(getenv("CRG_GEMM_RING")) : 1;
   static const int min_pct = getenv("CRG_GEMM_RING_MIN") ? atoi(getenv("CRG_GEMM_RING_MIN")) : 300;  // dev knob: least tiles, % of the CU count
   if (!on || batch != 1 || p.K % 64 || p.K < 128 || p.splits != 1) return false;
@@ -481,11 +483,16 @@ bool ring_gemm_ok(const GemmP& p, int batch, int n_cu) {
   if (geglu ? (p.N % 32 || (p.ldy & 3)) : (p.N % 8 || (p.ldy & 7) || ((uintptr_t)p.y & 15))) return false;
   if (p.res && ((p.ldr & 7) || ((uintptr_t)p.res & 15))) return false;
   if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-  const double lim = 2147483648.0;
-  if ((double)p.M * p.lda * 2 >= lim || (double)p.N * p.ldw * 2 >= lim || (double)p.M * p.ldy * 2 >= lim || (p.res && (double)p.M * p.ldr * 2 >= lim)) return false;
+  if ((double)p.N * p.ldw * 2 >= 2147483648.0) return false;
   const int bn = (!geglu && p.N % 160 == 0) ? 160 : 128;
-  const long tiles = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
+  const long tiles = ((heur_M + 255) / 256) * ((p.N + bn - 1) / bn);
   return tiles * 100 >= (long)(n_cu > 0 ? n_cu : 256) * min_pct;
+}
+
+// every extent that grows with the rows of the CALL addressable through a 32-bit buffer descriptor
+bool ring_gemm_fits(const GemmP& p) {
+  const double lim = 2147483648.0;
+  return !((double)p.M * p.lda * 2 >= lim || (double)p.M * p.ldy * 2 >= lim || (p.res && (double)p.M * p.ldr * 2 >= lim));
 }
 
 int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops, double bytes) {

@@ -572,7 +572,8 @@ __device__ __forceinline__ void wait_vmcnt() {  // s_waitcnt vmcnt(N) only (expc
 // apart (bf16), launched in place of conv3_rowhalo_kernel<.., MT = 2>
 int launch_conv_pp(crg_ctx* ctx, hipStream_t st, const GemmP& p, int wnt);
 // gemm_ring.hip: persistent 256-row-tile GEMM (bf16, plain / GEGLU epilogue), launched in place of gemm_glds_kernel where it applies
-bool ring_gemm_ok(const GemmP& p, int batch, int n_cu);
+bool ring_gemm_ok(const GemmP& p, int batch, int n_cu, long heur_M);
+bool ring_gemm_fits(const GemmP& p);
 int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& p, double flops, double bytes);
 
 }  // namespace crg_mm

@@ -538,10 +538,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
 }
 
 template <typename T>
-static void launch_layernorm(hipStream_t st, const T* x, const float* gamma, const float* beta, T* y, long rows, int dim, float eps) {
+static void launch_layernorm(hipStream_t st, const T* x, const float* gamma, const float* beta, T* y, long rows, int dim, float eps, bool invariant) {
   const int nchunks = (dim / 8 + 63) / 64;
   // few rows: one row per wave so that the grid still covers the chip; many rows: at most 8 blocks per CU, the waves loop
-  const bool small = rows < 4 * 256 * 8;
+  // (batch-invariant mode: the call does not know its rows per sample, so the grouping is the one-row form whatever the row count)
+  const bool small = invariant || rows < 4 * 256 * 8;
   static const int bpc = getenv("CRG_LN_BPC") ? atoi(getenv("CRG_LN_BPC")) : 8;  // dev knob: resident blocks per CU
 #define CRG_LN(NCH, RW)                                                                                                     \
   do {                                                                                                                      \
@@ -621,10 +622,12 @@ static int groupnorm_impl(crg_ctx* ctx, void* stream, const void* x, const void*
   }
   // rows per block: ~64 rows each (the per-block reduction epilogue is the fixed cost), at most 256 chunks per sample (the apply prologue re-reduces them),
   // and at least ~512 blocks over the chip when the image is large enough
+  // (batch-invariant mode: "the chip is full" is judged for tune_samples samples, crg_heur_samples - the chunking decides how a sample's
+  // partial sums are grouped)
   int chunks = HW / 64;
   if (chunks < 1) chunks = 1;
   if (chunks > 256) chunks = 256;
-  while ((long)chunks * N < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
+  while ((long)chunks * crg_heur_samples(ctx, N) < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
   if (chunks < 1) chunks = 1;
   const int rpc = (HW + chunks - 1) / chunks;
   chunks = (HW + rpc - 1) / rpc;
@@ -702,7 +705,7 @@ extern "C" int crg_groupnorm_pre(crg_ctx* ctx, void* stream, const void* x, cons
     int chunks = HW / 64;
     if (chunks < 1) chunks = 1;
     if (chunks > 256) chunks = 256;
-    while ((long)chunks * N < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
+    while ((long)chunks * crg_heur_samples(ctx, N) < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
     const int rpc = (HW + chunks - 1) / chunks;
     chunks = (HW + rpc - 1) / rpc;
     crg_prof_scope ps(ctx, st, CRG_K_GN_APPLY, 5.0 * elems, elems * 4.0);
@@ -740,7 +743,7 @@ extern "C" int crg_groupnorm_pre_split(crg_ctx* ctx, void* stream, const void* x
     int chunks = HW / 64;
     if (chunks < 1) chunks = 1;
     if (chunks > 256) chunks = 256;
-    while ((long)chunks * N < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
+    while ((long)chunks * crg_heur_samples(ctx, N) < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
     const int rpc = (HW + chunks - 1) / chunks;
     chunks = (HW + rpc - 1) / rpc;
     crg_prof_scope ps(ctx, st, CRG_K_GN_APPLY, 5.0 * elems, elems * 8.0);
@@ -776,7 +779,7 @@ extern "C" int crg_groupnorm_mx(crg_ctx* ctx, void* stream, const void* x, const
     int chunks = HW / 64;
     if (chunks < 1) chunks = 1;
     if (chunks > 256) chunks = 256;
-    while ((long)chunks * N < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
+    while ((long)chunks * crg_heur_samples(ctx, N) < 512 && chunks * 8 <= HW && chunks < 256) chunks *= 2;
     const int rpc = (HW + chunks - 1) / chunks;
     chunks = (HW + rpc - 1) / rpc;
     crg_prof_scope ps(ctx, st, CRG_K_GN_APPLY, 5.0 * elems, elems * 8.0);
@@ -806,9 +809,9 @@ extern "C" int crg_layernorm(crg_ctx* ctx, void* stream, const void* x, const fl
   const double elems = (double)rows * dim;
   crg_prof_scope ps(ctx, st, CRG_K_LAYERNORM, 8.0 * elems, elems * crg_dtype_size(dtype) * 2);
   if (dtype == CRG_BF16)
-    launch_layernorm<bf16>(st, (const bf16*)x, gamma, beta, (bf16*)y, (long)rows, dim, eps);
+    launch_layernorm<bf16>(st, (const bf16*)x, gamma, beta, (bf16*)y, (long)rows, dim, eps, ctx->invariant > 0);
   else if (dtype == CRG_F32)
-    launch_layernorm<float>(st, (const float*)x, gamma, beta, (float*)y, (long)rows, dim, eps);
+    launch_layernorm<float>(st, (const float*)x, gamma, beta, (float*)y, (long)rows, dim, eps, ctx->invariant > 0);
   else
     return crg_fail(ctx, -22, "layernorm: dtype %d unsupported", dtype);
   CRG_CHECK_LAUNCH(ctx, "layernorm");

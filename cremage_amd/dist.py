@@ -12,6 +12,11 @@ this is new functionality named by BASELINE.json's north_star:
     decode is ~7 % of the FLOPs and parallelises perfectly);
   * NO per-step communication and no tensor-parallel split of the UNet.
 
+Sharded == unsharded BITWISE only under the batch-invariant mode (cremage_amd.set_batch_invariant / CRG_BATCH_INVARIANT): per-image
+generators make every rank draw the noise the unsharded batch draws, but by default the kernels a rank runs are picked from the size
+of ITS batch, so the last bits of an image depend on how the batch was cut; with the mode on, an image's bits are a function of the
+image, the weights and tune_samples (tests/test_batch_invariant_gpu.py runs shards of (3), (2, 1) and (1, 1, 1) against each other).
+
 Everything here also runs on the `gloo` backend with CPU tensors (tests/test_dist_cpu.py).
 """
 from __future__ import annotations

@@ -759,6 +759,17 @@ def _gemm(h, **kw):
     L.check(L.load().crg_gemm(h, _st(), C.byref(a)), h, "crg_gemm")
 
 
+def rows_per_sample(x: torch.Tensor, gn_hw: Optional[int] = None) -> int:
+    """crg_gemm_args.rows_per_sample of a GEMM over the last dim of x (read under the batch-invariant mode only): the rows of one
+    sample - gn_hw where the caller names the image size, T for [B, T, K] tokens (every dim between the first and the last), 1 for
+    2-D inputs such as the hoisted time rows, whose rows are samples."""
+    if gn_hw:
+        return int(gn_hw)
+    if x.dim() <= 2:
+        return 1
+    return int(math.prod(x.shape[1:-1]))
+
+
 def last_route(device: Optional[int] = None) -> dict:
     """What the last crg_gemm / crg_conv2d call on the device's context decided (crg_last_route, include/crg_hip.h): a plain dict with
     `kernel` in L.ROUTE_KERNELS, `reduce` in L.ROUTE_REDUCES and the other fields of crg_route as integers.  Host bookkeeping: reads
@@ -830,6 +841,7 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
         if residual.shape != y.shape or residual.dtype != y.dtype:
             raise L.CrgError("linear: residual must match the output in shape and dtype")
     h = _h(x)
+    rps = rows_per_sample(x, gn_hw)
     stats = _gn_stats_buffer(M, N, gn_hw, x.dtype, out_dtype, x.device) if not geglu else None
     rs = None
     if row_stats and LN_EPI and stats is None and ln is None and act is None and vt is None and x.dtype == HALF and out_dtype == HALF and N % 8 == 0 \
@@ -845,7 +857,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
           vt=vt.data_ptr() if vt is not None else None, vt_n0=transposed_from or 0, vt_tokens=vt_tokens, vt_ld=vt_ld,
           row_stats=rs.data_ptr() if rs is not None else None, row_stats_parts=rs.shape[1] if rs is not None else 0,
           ln_stats=ln_stats.data_ptr() if ln_stats is not None else None, ln_parts=ln_stats.shape[1] if ln_stats is not None else 0,
-          ln_colsum=ln_s.data_ptr() if ln_s is not None else None, ln_eps=float(ln[2]) if ln is not None else 0.0)
+          ln_colsum=ln_s.data_ptr() if ln_s is not None else None, ln_eps=float(ln[2]) if ln is not None else 0.0,
+          rows_per_sample=rps)
     if stats is not None:
         y._crg_gn_pending = stats  # the caller that shapes y into an image attaches it (image_of_stats)
     if rs is not None:
@@ -896,10 +909,11 @@ def ln_linear_ok(x: torch.Tensor, weight: torch.Tensor, act: Optional[str] = Non
         if geglu or x.dim() != 3 or not (0 < transposed_from < N) or transposed_from % bn:
             return False
         ld = (x.shape[1] + 7) // 8 * 8
-        if x.shape[0] * (N - transposed_from) * ld * 2 >= (1 << 31):
+        if x.shape[0] * (N - transposed_from) * ld * 2 >= (1 << 31) and not L.invariant():
             return False
         n_out = transposed_from
-    return max(M * 320, N * 320, M * n_out) * 2 < (1 << 31)
+    # (batch-invariant mode: the 2 GiB clauses read the size of the whole call, so there they are crg_ln_gemm's errors, not another route)
+    return L.invariant() > 0 or max(M * 320, N * 320, M * n_out) * 2 < (1 << 31)
 
 
 def ln_linear(x: torch.Tensor, ln_weight, ln_bias, eps: float, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -969,6 +983,7 @@ def linear_transposed(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
               bias=b.data_ptr() if b is not None else None, bias_mode=L.BIAS_ROW if b is not None else L.BIAS_NONE,
               residual=None, ldr=0, r_bstride=0, y=y.data_ptr(), ldy=ld, y_bstride=N * ld, M=N, N=T, K=K, batch=B,
               epilogue=L.EPI_NONE, a_dtype=L.BF16, y_dtype=L.BF16, prec=L.PREC_BF16, a_is_weight=1, a_lo=None)
+        # (a_is_weight: the samples lie along `batch` and the rows are the weight's, so rows_per_sample is not read: left 0)
     else:
         # fp32 activations cannot sit on the pre-split W side: split them once on the fly (crg_split_bf16, no torch arithmetic)
         xh, xl = torch.empty(x.shape, dtype=HALF, device=x.device), torch.empty(x.shape, dtype=HALF, device=x.device)
@@ -1272,7 +1287,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
             _gemm(h, a=q[b, q0:].data_ptr(), lda=Cc, a_bstride=Dh, w=kh[b].data_ptr(), w_lo=kl[b].data_ptr() if split else None, ldw=Cc,
                   w_bstride=Dh, bias=None, bias_mode=L.BIAS_NONE, residual=None, ldr=0, r_bstride=0, y=sv.data_ptr(), ldy=kp,
                   y_bstride=ld_s, M=nq, N=n_keys, K=Dh, batch=heads, epilogue=L.EPI_NONE, a_dtype=_act_dt(q), y_dtype=L.F32,
-                  prec=prec, a_is_weight=0, a_lo=None)
+                  prec=prec, a_is_weight=0, a_lo=None, rows_per_sample=nq)  # (the call lies inside one sample)
             if nq == s.shape[1]:
                 softmax_rows_(s, n_keys, scale)
             else:  # last, shorter chunk: the rows of one head are contiguous [nq, kp]
@@ -1281,7 +1296,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
             _gemm(h, a=sv.data_ptr(), lda=kp, a_bstride=ld_s, w=vh[b].data_ptr(), w_lo=vl[b].data_ptr() if split else None, ldw=ld,
                   w_bstride=Dh * ld, bias=None, bias_mode=L.BIAS_NONE, residual=None, ldr=0, r_bstride=0, y=o[b, q0:].data_ptr(), ldy=Cc,
                   y_bstride=Dh, M=nq, N=Dh, K=kp, batch=heads, epilogue=L.EPI_NONE, a_dtype=L.F32, y_dtype=_act_dt(q), prec=prec,
-                  a_is_weight=0, a_lo=None)
+                  a_is_weight=0, a_lo=None, rows_per_sample=nq)
     return o
 
 

@@ -29,6 +29,9 @@
 extern "C" {
 #endif
 
+/* 104 since the route record.  The batch-invariant mode (crg_ctx_set_invariant / crg_ctx_get_invariant and the trailing
+ * crg_gemm_args.rows_per_sample) was added without a version step: two new symbols and one trailing field that is ignored while the
+ * mode is off, so every caller built in this tree against 104 keeps working unchanged. */
 #define CRG_VERSION 104
 
 typedef struct crg_ctx crg_ctx;
@@ -70,6 +73,20 @@ void crg_ctx_destroy(crg_ctx* ctx);
 const char* crg_last_error(crg_ctx* ctx);
 /* Pre-size the context's scratch (GroupNorm partial statistics, split-K slabs). Synchronous. */
 int crg_ctx_reserve(crg_ctx* ctx, size_t bytes);
+/* Batch-invariant mode.  tune_samples = 0 (the state of a new context): off.  tune_samples >= 1: every decision of this library that
+ * changes WHICH floating-point operations produce an output element, or their order - kernel family, tile configuration, K slices
+ * and their boundaries, reduce kernel, tail split, 32- or 256-row statistics partials, GroupNorm chunking, attention kernel, LayerNorm
+ * rows per wave - is taken from the PER-SAMPLE problem (rows per sample, N, K, kernel size, stride, epilogue, side channels, dtypes,
+ * precision, heads, head dim) and from tune_samples alone: a size heuristic reads tune_samples * rows_per_sample where it reads the
+ * call's size today.  Never from the number of samples in the call, a sample's index or what else shares the launch; the launch itself
+ * (grid, XCD partition, tile order) stays that of the real size.  The result for one sample is then a function of that sample, the
+ * weights and tune_samples: bit-identical alone, at any position of any batch, and on any rank of a sharded run.  The tail split is off
+ * under the mode; a route whose buffer descriptors cannot address the real call is an error there, not another route.
+ * Entry points with one kernel per problem class and one block per fixed tile of one sample's rows take no such decision and are
+ * invariant with the mode on or off: crg_ln_gemm, crg_gemm_mx8 / crg_quant_mx8, crg_attention_x3, crg_softmax_rows, crg_conv_small.
+ * Host bookkeeping only: no launch, no synchronisation.  The getter returns tune_samples (0 = off). */
+int crg_ctx_set_invariant(crg_ctx* ctx, int tune_samples);
+int crg_ctx_get_invariant(crg_ctx* ctx);
 
 /* ---- per-kernel timing (bench.py roofline: HIP events on the launch stream) ------------ */
 /* Between begin/end every kernel launched by a crg_* call is bracketed by hipEvents on its launch stream and
@@ -220,6 +237,10 @@ typedef struct {
    * variance as nn.LayerNorm).  The normalised tensor never exists and no LayerNorm launch runs.  K = the LayerNorm width. */
   float* row_stats; int row_stats_parts;
   const float* ln_stats; int ln_parts; const float* ln_colsum; float ln_eps;
+  /* batch-invariant mode only (ignored while it is off): rows of M that belong to one sample - T for [B][T][K] tokens, H * W for a
+   * 1x1 conv, M itself for a call that lies inside one sample; M must be a multiple of it.  0 means 1: the route then depends on N, K
+   * and the flags only (always invariant, possibly slow).  With a_is_weight the samples lie along `batch` and the field is unused. */
+  int rows_per_sample;
 } crg_gemm_args;
 int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* args);
 
