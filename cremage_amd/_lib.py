@@ -187,6 +187,29 @@ class AttnX3Args(C.Structure):
     ]
 
 
+class ConvFramesArgs(C.Structure):
+    _fields_ = [
+        ("x", c_void_p), ("w", c_void_p),
+        ("bias", c_void_p),
+        ("cvec", c_void_p), ("cvec_ld", c_int64),
+        ("residual", c_void_p), ("rscale", c_void_p),
+        ("y", c_void_p),
+        ("b", c_int), ("T", c_int), ("S", c_int), ("Cin", c_int), ("Cout", c_int),
+    ]
+
+
+class AttnFramesArgs(C.Structure):
+    _fields_ = [
+        ("q", c_void_p), ("ldq", c_int64),
+        ("k", c_void_p), ("ldk", c_int64),
+        ("v", c_void_p), ("ldv", c_int64),
+        ("o", c_void_p), ("ldo", c_int64),
+        ("b", c_int), ("T", c_int), ("S", c_int), ("H", c_int), ("Dh", c_int),
+        ("scale", c_float),
+        ("dtype", c_int),
+    ]
+
+
 ROUTE_KERNELS = ["none", "glds", "rowhalo", "conv_pp", "gemm_ring", "gemm_reg", "planes"]  # enum crg_route_kernel
 ROUTE_REDUCES = ["none", "plain", "stats", "rows", "gn"]  # enum crg_route_reduce
 
@@ -266,6 +289,10 @@ SIGNATURES = {
     "crg_pack_weight_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "crg_gemm_mx8": (c_int, [c_void_p, c_void_p, C.POINTER(Mx8GemmArgs)]),
     "crg_attention_x3": (c_int, [c_void_p, c_void_p, C.POINTER(AttnX3Args)]),
+    "crg_conv_frames": (c_int, [c_void_p, c_void_p, C.POINTER(ConvFramesArgs)]),
+    "crg_attention_frames": (c_int, [c_void_p, c_void_p, C.POINTER(AttnFramesArgs)]),
+    "crg_add_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int]),
+    "crg_lincomb_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int]),
 }
 
 

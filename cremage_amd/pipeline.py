@@ -377,6 +377,44 @@ def build_synthetic_sdxl_refiner(unet_cfg=None, vae_dd=None, device="cuda", unet
     return eng.to(device).eval()
 
 
+# svd_xt_1_1.yaml network_config (scripts/sampling/configs): the SVD-XT video UNet
+SVD_XT_UNET = dict(adm_in_channels=768, num_classes="sequential", use_checkpoint=True, in_channels=8, out_channels=4, model_channels=320,
+                   attention_resolutions=[4, 2, 1], num_res_blocks=2, channel_mult=[1, 2, 4, 4], num_head_channels=64,
+                   use_linear_in_transformer=True, transformer_depth=1, context_dim=1024, spatial_transformer_attn_type="softmax-xformers",
+                   extra_ff_mix_layer=True, use_spatial_context=True, merge_strategy="learned_with_images", video_kernel_size=[3, 1, 1])
+
+
+def build_synthetic_svd(unet_cfg=None, device="cuda", unet_dtype=torch.bfloat16, seed: int = 1234, fill: bool = True):
+    """The SVD-XT video UNet (cremage_amd.sgm_hip.video.VideoUNet, 1.52 B parameters at the default configuration) with name-keyed
+    synthetic weights.  The network alone: its inputs - CLIP image embedding, VAE-encoded conditioning frames, the fps / motion /
+    augmentation vector - are the caller's tensors, and the latent frames it denoises go to the reference's VideoDecoder."""
+    from .sgm_hip.video import VideoUNet
+    unet = VideoUNet(**(unet_cfg or SVD_XT_UNET))
+    if fill:
+        synth_fill_(unet, seed, prefix="svd_unet.")
+    return unet.to(unet_dtype).to(device).eval()
+
+
+@torch.no_grad()
+def img2vid_latents(engine, c: dict, uc: dict, *, num_frames: int, steps: int = 30, min_scale: float = 1.0, max_scale: float = 2.5,
+                    height: int = 576, width: int = 1024, x0: Optional[torch.Tensor] = None, seed: int = 0,
+                    sigma_max: float = 700.0) -> torch.Tensor:
+    """The Video Generator's sampling call (svd_video_generator.py: EulerEDMSampler on EDMDiscretization, LinearPredictionGuider,
+    VScalingWithEDMcNoise) on the HIP VideoUNet `engine` (build_synthetic_svd, or a loaded one): returns the latent frames
+    [(b t), 4, height / 8, width / 8] for the reference's VideoDecoder.  c / uc: "crossattn" [(b t), M, 1024], "vector" [(b t), 768],
+    "concat" [(b t), 4, h, w]; `x0`: unit-variance start noise (default: torch.randn from `seed`)."""
+    from .sgm_hip.video_sampling import sample_video_latents
+    frames = c["crossattn"].shape[0]
+    if frames % num_frames:
+        raise ValueError(f"img2vid_latents: {frames} conditioning rows are no whole number of videos of {num_frames} frames")
+    dev = c["crossattn"].device
+    if x0 is None:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        x0 = torch.randn((frames, 4, height // 8, width // 8), generator=g).to(dev)
+    return sample_video_latents(engine, x0.float(), c, uc, num_frames=num_frames, steps=steps, min_scale=min_scale, max_scale=max_scale,
+                                sigma_max=sigma_max)
+
+
 @torch.no_grad()
 def txt2img_sdxl(eng, c: dict, uc: dict, *, steps: int = 30, cfg_scale: float = 5.0, height: int = 1024, width: int = 1024,
                  x0: Optional[torch.Tensor] = None, decode: bool = True, sampler: str = "euler_edm", stage2strength: Optional[float] = None,

@@ -707,6 +707,53 @@ typedef struct {
 } crg_attn_x3_args;
 int crg_attention_x3(crg_ctx* ctx, void* stream, const crg_attn_x3_args* args);
 
+/* ---- temporal layers of the video UNet (video.hip) ----------------------------------------------------------------------------------------
+ * Activations are [b*T*S][C] rows: video v, frame t, pixel s at row (v*T + t)*S + s - the bytes of a [(b t), h, w, C] channels-last tensor.
+ *
+ * crg_conv_frames: the (3, 1, 1) conv along the frame axis,
+ *     y[v,t,s,:] = sum_{d=-1,0,1} W_d x[v,t+d,s,:] + bias [+ cvec[v*T+t,:]],   then, with a residual,  y = residual + rscale[v*T+t] * y
+ *   (rscale NULL = 1).  Frames outside [0, T) contribute zero BY SELECTION: their rows - another video's, or outside the tensor - are never
+ *   read, so a NaN there cannot reach y.  x half type [b*T*S][Cin]; w half type [Cout][3*Cin], tap-major (column d*Cin + c = weight
+ *   [o][c][d][0][0]; crg_pack_weight CRG_PACK_LINEAR of that permuted matrix); bias fp32 [Cout] or NULL; cvec fp32 [b*T][cvec_ld] or NULL;
+ *   residual half type [b*T*S][Cout] or NULL; rscale fp32 [b*T] or NULL (needs residual); y half type [b*T*S][Cout], may alias residual.
+ *   fp32 accumulation over the whole K = 3*Cin in one block, fixed order; the tile shape depends on Cout alone: a row's bits are a function
+ *   of its own video and the weights, with the batch-invariant mode on or off.
+ *   Domain: Cin, Cout multiples of 32; b, T, S >= 1; b*T*S < 2^31 - 128; all pointers 16-byte aligned; cvec_ld >= Cout, a multiple of 4.
+ *   Profile slot: CRG_K_CONV_W4 (128-wide tiles) / CRG_K_CONV_W1.
+ *
+ * crg_attention_frames: for every (video, pixel, head)  o = softmax(q k^T * scale) v  over the T frames.  q, k, v: `dtype` (CRG_BF16 = the
+ *   half type, or CRG_F32) [b*T*S][ld*], head h at column h*Dh - column ranges of one fused projection output, V row-major; o `dtype`
+ *   [b*T*S][ldo].  Products, softmax and sums in fp32 on the vector unit.  One kernel per (dtype, head-width class), no decision from b.
+ *   Domain: 1 <= T <= 32 (more frames: -22), Dh a multiple of 8 in 8..64, b <= 65535, row strides >= H*Dh and multiples of 16 bytes,
+ *   pointers 16-byte aligned.  Profile slot: CRG_K_ATTN.
+ *
+ * crg_add_frames:     y[r][:] = x[r][:] + e[r / S][:]             x, y `dtype` [frames*S][C], e `dtype` [frames][C]; C % 8 == 0; y may be x.
+ * crg_lincomb_frames: y = a[f] * x + c[f] * z per frame f         x, z, y `dtype` [frames][per_frame] dense, a / c fp32 [frames] or NULL (= 1,
+ *   product skipped); per_frame % 8 == 0.  Each product and the sum are rounded separately in fp32 (no FMA), then once to `dtype`.
+ *   Profile slot of both: CRG_K_ELEMENTWISE. */
+typedef struct {
+  const void* x; const void* w;
+  const float* bias;
+  const float* cvec; int64_t cvec_ld;
+  const void* residual; const float* rscale;
+  void* y;
+  int b, T, S, Cin, Cout;
+} crg_conv_frames_args;
+int crg_conv_frames(crg_ctx* ctx, void* stream, const crg_conv_frames_args* args);
+typedef struct {
+  const void* q; int64_t ldq;
+  const void* k; int64_t ldk;
+  const void* v; int64_t ldv;
+  void* o; int64_t ldo;
+  int b, T, S, H, Dh;
+  float scale;
+  int dtype;
+} crg_attn_frames_args;
+int crg_attention_frames(crg_ctx* ctx, void* stream, const crg_attn_frames_args* args);
+int crg_add_frames(crg_ctx* ctx, void* stream, const void* x, const void* e, void* y, int64_t frames, int S, int C, int dtype);
+int crg_lincomb_frames(crg_ctx* ctx, void* stream, const float* a, const void* x, const float* c, const void* z, void* y, int64_t frames,
+                       int64_t per_frame, int dtype);
+
 #ifdef __cplusplus
 }
 #endif
