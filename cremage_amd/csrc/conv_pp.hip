@@ -486,7 +486,7 @@ extern "C" int crg_debug_read_pp(unsigned long long* dst, int n) {
 namespace crg_mm {
 #endif
 
-// Host entry (called from gemm_conv.hip's launch_kernel in place of the 2-stage 256-row kernel): bf16 in / bf16 out.
+// Host entry (called from gemm_conv.hip's launch_one in place of the 2-stage 256-row kernel): bf16 in / bf16 out.
 int launch_conv_pp(crg_ctx* ctx, hipStream_t st, const GemmP& p, int wnt) {
   void (*kern)(GemmP) = nullptr;
   const bool lin = p.halo_lin != 0;

@@ -52,7 +52,6 @@ struct crg_ctx {
   void* zero_page = nullptr;  // 4 KiB of zeros: LDS-DMA source for conv padding and tile tails
   std::vector<const void*> lds_attr;  // kernels whose dynamic-LDS limit was raised ON THIS CONTEXT'S DEVICE (crg_set_dyn_lds)
   crg_route route = {};  // what the last crg_gemm / crg_conv2d decided (crg_last_route)
-  bool gn_fused = false;  // set by the split-K reduce launch when it also ran the GroupNorm behind the conv (crg_conv_args.gn_y)
   bool profiling = false;
   std::vector<crg_prof_rec> recs;
   std::vector<hipEvent_t> event_pool;

@@ -1492,490 +1492,201 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(GemmP p) {
   }
 }
 
-// can the reduce behind this split-K launch also run the GroupNorm the caller asked for?
-template <typename YT>
-bool gn_slab_ok(const GemmP& p, int batch) {
-  if (sizeof(YT) != 2 || !p.gn_y || !p.gn_gamma || !p.gn_beta || batch != 1 || p.slab_row0 != 0 || p.gstat || p.vt || p.rstat) return false;
-  if (p.epi != CRG_EPI_NONE || (p.bias_mode != CRG_BIAS_NONE && p.bias_mode != CRG_BIAS_COL)) return false;
-  if (p.gn_groups <= 0 || p.N % p.gn_groups || p.gn_hw <= 0 || p.M % p.gn_hw || p.ldy != p.N) return false;
-  const int gs = p.N / p.gn_groups;
-  if (gs % 8 || (p.N & 7) || (p.res && (p.ldr & 7)) || (p.cvec && (p.cvec_ld & 3))) return false;
-  return (long)p.gn_hw * (gs >> 3) <= 256 * 8;
-}
+// ---- the launcher ------------------------------------------------------------------------------------------------------------------
+// Every size decision is the planner's (gemm_plan.h): what follows fills GemmP from the plan, picks the kernel pointer from the plan's
+// selectors - one switch per kernel family - and launches.
+using crg_plan::Launch;
+using crg_plan::Plan;
+typedef void (*KernFn)(GemmP);
 
-// the reduce launch behind a split-K launch (whole problem, or - tail split - the rows >= slab_row0)
-template <typename YT>
-int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, int batch) {
-  const long rows = p.M - p.slab_row0;
-  crg_prof_scope ps(ctx, st, CRG_K_SPLITK, (double)batch * p.splits * rows * p.N, (double)batch * rows * p.N * (4.0 * p.splits + sizeof(YT)));
-  if (gn_slab_ok<YT>(p, batch)) {
-    const int vpt = (int)(((long)p.gn_hw * (p.N / p.gn_groups >> 3) + 255) / 256);
-    const dim3 grid(p.gn_groups, p.M / p.gn_hw);
-    switch (vpt) {
-      case 1: hipLaunchKernelGGL(splitk_reduce_gn_kernel<1>, grid, dim3(256), 0, st, p); break;
-      case 2: hipLaunchKernelGGL(splitk_reduce_gn_kernel<2>, grid, dim3(256), 0, st, p); break;
-      case 3: hipLaunchKernelGGL(splitk_reduce_gn_kernel<3>, grid, dim3(256), 0, st, p); break;
-      case 4: hipLaunchKernelGGL(splitk_reduce_gn_kernel<4>, grid, dim3(256), 0, st, p); break;
-      case 5: hipLaunchKernelGGL(splitk_reduce_gn_kernel<5>, grid, dim3(256), 0, st, p); break;
-      case 6: hipLaunchKernelGGL(splitk_reduce_gn_kernel<6>, grid, dim3(256), 0, st, p); break;
-      default: hipLaunchKernelGGL(splitk_reduce_gn_kernel<8>, grid, dim3(256), 0, st, p); break;
+// gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, PAIR, XT>: the epilogues that exist for (YT, CONV)
+template <int WNT, typename YT, bool CONV, int STAGES, int WMT, int KG>
+KernFn pick_glds_epilogue(const Launch& L) {
+  if constexpr (sizeof(YT) == 2) {
+    if constexpr (!CONV) {
+      if (L.xt == 3) return L.pair ? gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 3> : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, false, 3>;
+      if (L.xt == 2) return gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 2>;
     }
-    CRG_CHECK_LAUNCH(ctx, "splitk_reduce_gn");
-    ctx->gn_fused = true;
-    ctx->route.reduce = CRG_REDUCE_GN;
-    return 0;
+    if (L.xt == 1) return gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 1>;
+    if (L.pair) return gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true>;
   }
-  if (p.rstat) {
-    if (sizeof(YT) != 2 || batch != 1 || (p.N & 3) || (p.ldy & 3) || p.epi != CRG_EPI_NONE || p.cvec || p.rstat_parts > 64 || (p.res && (p.ldr & 3)))
-      return crg_fail(ctx, -22, "gemm: LayerNorm row statistics behind split-K need an unbatched plain bf16 problem with 4-aligned N / ldy / ldr");
-    const long blocks = (rows + 3) / 4;
-    hipLaunchKernelGGL(splitk_reduce_rows_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, p);
-    ctx->route.reduce = CRG_REDUCE_ROWS;
-  } else if (p.gstat) {
-    if (batch != 1 || (p.N & 3) || (p.ldy & 3) || (p.slab_row0 & 31) || (p.res && (p.ldr & 3)))
-      return crg_fail(ctx, -22, "gemm: GroupNorm statistics need an unbatched problem with 4-aligned N / ldy / ldr");
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel<YT>, dim3((unsigned)((rows + 31) / 32), (unsigned)((p.N + 127) / 128)), dim3(256), 0, st, p);
-    ctx->route.reduce = CRG_REDUCE_STATS;
-  } else {
-    const long total4 = rows * (p.N >> 2);
-    const int rg = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
-    hipLaunchKernelGGL(splitk_reduce_kernel<YT>, dim3(rg, batch), dim3(256), 0, st, p);
-    ctx->route.reduce = CRG_REDUCE_PLAIN;
+  return gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG>;
+}
+
+template <int WNT, typename YT, bool CONV>
+KernFn pick_glds(const Launch& L) {
+  if (L.ns == 2) {  // pre-split planes: 8 waves in two k-groups
+    if constexpr (sizeof(YT) == 4) return gemm_glds_kernel<WNT, float, CONV, 2, 4, 2, 2>;
+    return nullptr;
   }
-  CRG_CHECK_LAUNCH(ctx, "splitk_reduce");
-  return 0;
-}
-
-// Split-K factor: small-M problems (8x8 / 16x16 UNet levels, token GEMMs with few rows) launch far fewer
-// than 2 blocks per CU and stream long K; cut K so that ~512 blocks are in flight, keeping >= 8 k-tiles
-// per slice.  Costs one fp32 slab round trip + one extra launch, so only when the tile count is low.
-// `blocks`: tiles x batch as the size heuristics count them (heur_blocks: the call's own, or those of tune_samples samples under the
-// batch-invariant mode)
-inline int choose_splits(const GemmP& p, long blocks) {
-  if (p.epi == CRG_EPI_GEGLU || (p.N & 3) || p.ln_stat) return 1;  // (the LayerNorm correction is per whole row sum: no K slices)
-  const int nk = (p.K + BK - 1) / BK;
-  // 256..511 blocks leave one block (4 waves) on most CUs, which hides neither the barrier nor the DMA latency: cut K in
-  // two when it is long enough to amortise the slab pass (measured: 8x32x32 640->640 conv 112 -> 89 us, 1280->640 203 -> 137 us;
-  // K = 2560 GEMMs lose 5 %, hence the nk bound)
-  // short K (nk < 24) is not split: measured slower than the 64-row / 8-wave configuration on the unsplit problem
-  // (128..255 tiles with a K of 24..63 k-tiles - the 16x16-level 1x1 skip convs over a concat, 2048 x 1280 x 1920 / 2560 - are faster
-  // unsplit on the 64-row / 8-wave configuration: 30.3 -> 24.0 us and 33.6 -> 30.5 us, tools/c1_probe.py, round 3)
-  if (blocks >= 512 || nk < 24 || (blocks >= 128 && nk < 64)) return 1;
-  int s;
-  if (blocks >= 256) {
-    // one to two blocks per CU and a long K: among 2..4 slices take the one whose blocks fill whole rounds of 512 best
-    // (256 tiles -> 2, 288 tiles (768x768 latents at the 48x48 level) -> 3, 384 -> 4); ties go to fewer slices
-    s = 2;
-    double best = 1e9;
-    for (int c = 2; c <= 4; ++c) {
-      const double t = (double)((blocks * c + 511) / 512) / c;
-      if (t < best - 1e-9) {
-        best = t;
-        s = c;
-      }
-    }
-    return s;
-  }
-  static const int tgt = getenv("CRG_SPLIT_BLOCKS") ? atoi(getenv("CRG_SPLIT_BLOCKS")) : 512;  // dev knob: blocks aimed at by the K cut
-  static const int smax = getenv("CRG_SPLIT_MAX") ? atoi(getenv("CRG_SPLIT_MAX")) : 16;          // dev knob: most K slices
-  s = (int)((tgt + blocks - 1) / blocks);
-  if (s > nk / 8) s = nk / 8;
-  if (s > smax) s = smax;
-  return s < 2 ? 1 : s;
-}
-
-// What the size heuristics of one call read (host only; built by heur_of for every call, so no entry point can inherit another call's):
-// the call's own rows and batch with the batch-invariant mode off; tune_samples samples of the per-sample problem with it on (rps =
-// rows per sample then, else 0).
-struct Heur {
-  long M;
-  int batch, rps;
-};
-
-inline Heur heur_of(const crg_ctx* ctx, long M, int batch, int rps, bool samples_along_batch) {
-  if (ctx->invariant <= 0) return Heur{M, batch, 0};
-  if (samples_along_batch) return Heur{M, ctx->invariant, 0};
-  return Heur{(long)ctx->invariant * rps, batch, rps};
-}
-
-// Blocks of `rows`-row tiles the size heuristics count: p.tiles_n x ceil(M / rows) x batch of the call itself - or, under the
-// batch-invariant mode, of tune_samples samples of the per-sample problem (Heur), so that no decision taken from it depends on how
-// many samples share the launch.  The launch itself always covers the real p.M.
-inline long heur_blocks(const Heur& h, const GemmP& p, int rows) {
-  return (long)p.tiles_n * ((h.M + rows - 1) / rows) * h.batch;
-}
-
-struct Work {  // algorithmic work of one call (profiler), operand footprints (XCD partition) and the sizes its heuristics read
-  double flops, bytes, a_bytes, w_bytes;
-  Heur heur;
-};
-
-// (xg_m, xg_n, xg_s): see block_to_tile.  Minimise fabric traffic xg_n*|A| + xg_m*|W| over the feasible factorizations of 8.
-inline void choose_xcd_partition(GemmP& p, const Work& wk) {
-  p.xg_m = p.xg_n = 1;
-  p.xg_s = 0;
-  double best = 0.0;
-  for (int gs = 8; gs >= 1; gs >>= 1) {
-    if (p.splits % gs) continue;
-    for (int gn = 1; gn * gs <= 8; gn <<= 1) {
-      const int gm = 8 / (gs * gn);
-      if (p.tiles_n % gn || p.tiles_m % gm) continue;
-      const double cost = gn * wk.a_bytes + gm * wk.w_bytes;
-      if (!p.xg_s || cost < best) {
-        best = cost;
-        p.xg_m = gm; p.xg_n = gn; p.xg_s = gs;
-      }
-    }
+  switch (L.cfg) {
+    case 3: return pick_glds_epilogue<WNT, YT, CONV, CRG_C_STAGES, 2, 2>(L);
+    case 4: return pick_glds_epilogue<WNT, YT, CONV, 2, 2, 1>(L);
+    default: return pick_glds_epilogue<WNT, YT, CONV, 2, 4, 1>(L);
   }
 }
 
-template <int WNT, int NSPLIT, typename AT, typename YT, bool CONV, int STAGES, int WMT, int KG>
-int launch_kernel(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
-  constexpr int BN = 32 * WNT;
-  constexpr bool GLDS = (NSPLIT == 1) && (sizeof(AT) == 2);
-  constexpr size_t lds = GLDS ? (size_t)STAGES * (32 * WMT + BN) * 128 + 1024 /* dummy-load target */ : (size_t)2 * NSPLIT * (BM + BN) * 128;
-  {
-    const int nk_total = (p.K + BK - 1) / BK;
-    p.ks_q = nk_total / p.splits;
-    p.ks_r = nk_total % p.splits;
+// conv3_rowhalo_kernel<WNT, YT, PAIR, NS, KG, MT, MX, TAPS>
+template <int WNT>
+KernFn pick_rowhalo(const Launch& L) {
+  if (L.y_f32)  // pre-split planes
+    return L.mx ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, true>
+                : L.taps == 2 ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, false, 2> : conv3_rowhalo_kernel<WNT, float, false, 2, 2>;
+  if (L.mt == 2) {
+    if (L.taps == 2) return L.pair ? conv3_rowhalo_kernel<WNT, bf16, true, 1, 1, 2, false, 2> : conv3_rowhalo_kernel<WNT, bf16, false, 1, 1, 2, false, 2>;
+    return L.pair ? conv3_rowhalo_kernel<WNT, bf16, true, 1, 1, 2> : conv3_rowhalo_kernel<WNT, bf16, false, 1, 1, 2>;
   }
-  p.pair = (GLDS && sizeof(YT) == 2 && p.splits == 1 && p.epi != CRG_EPI_GEGLU && (p.N & 7) == 0 && (p.ldy & 7) == 0 &&
-            (p.y_bs & 7) == 0 && ((uintptr_t)p.y & 15) == 0 &&
-            (!p.res || ((p.ldr & 7) == 0 && (p.r_bs & 7) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
-            (!p.cvec || (p.cvec_ld & 3) == 0)) ? 1 : 0;
-  if (p.vt && !(p.pair && p.splits == 1 && !p.gstat && !CONV))
-    return crg_fail(ctx, -22, "gemm: a transposed column range needs the paired bf16 epilogue of an unsplit, unbatched GEMM (N, ldy multiples of 8, K below the split-K rule)");
-  if (p.gstat && !p.pair && p.splits == 1)
-    return crg_fail(ctx, -22, "gemm/conv: GroupNorm statistics come from the paired bf16 epilogue (N, ldy, ldr multiples of 8, 16-byte aligned y / residual, no GEGLU)");
-  if (p.rstat && !(!p.gstat && !p.vt && !CONV && batch == 1 && sizeof(YT) == 2 && p.rstat_parts == 2 * p.tiles_n && p.epi == CRG_EPI_NONE &&
-                   ((p.splits == 1 && p.pair) || (p.splits > 1 && (p.N & 3) == 0 && (p.ldy & 3) == 0 && (!p.res || (p.ldr & 3) == 0)))))
-    return crg_fail(ctx, -22, "gemm: LayerNorm row statistics come from the paired bf16 epilogue of an unbatched plain GEMM (N, ldy multiples of 8) or from its split-K reduce, with row_stats_parts = 2 * ceil(N / tile) = %d (got %d)", 2 * p.tiles_n, p.rstat_parts);
-  if (p.ln_stat && !(GLDS && sizeof(YT) == 2 && !CONV && p.splits == 1 && batch == 1 && !p.res && !p.gstat && !p.rstat && !p.cvec && (p.N & 3) == 0 &&
-                     (p.bias_mode == CRG_BIAS_COL || p.bias_mode == CRG_BIAS_NONE) && (p.epi == CRG_EPI_NONE || p.epi == CRG_EPI_GEGLU)))
-    return crg_fail(ctx, -22, "gemm: the LayerNorm epilogue needs an unsplit, unbatched bf16 GEMM (N %% 4 == 0) without residual / statistics / SiLU");
-  void (*kern)(GemmP);
-  if constexpr (GLDS && sizeof(YT) == 2 && !CONV) {
-    if (p.ln_stat) kern = p.pair ? gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 3> : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, false, 3>;
-    else if (p.rstat && p.splits == 1) kern = gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 2>;
-    else
-      kern = p.pair ? ((p.gstat && p.splits == 1) ? gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 1> : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true>)
-                    : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG>;
-  } else if constexpr (GLDS && sizeof(YT) == 2)
-    kern = p.pair ? ((p.gstat && p.splits == 1) ? gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true, 1> : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG, 1, true>)
-                  : gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG>;
-  else if constexpr (GLDS) kern = gemm_glds_kernel<WNT, YT, CONV, STAGES, WMT, KG>;
-  else kern = gemm_kernel<WNT, NSPLIT, AT, YT, CONV, NSPLIT>;  // split-bf16: 8 waves (two k-groups)
-  size_t lds_bytes = lds;
-  bool halo = false;
-  int threads = GLDS ? 256 * KG : 256 * NSPLIT;
-  if constexpr (GLDS && CONV && STAGES == 2 && WMT == 4 && KG == 1 && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
-    static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 2;  // dev knob: 0 = plain implicit GEMM
-    const bool up2 = p.up == 2;  // sub-pixel form: groups of two k-tiles, geometry of the source grid, this kernel only (no knob)
-    const int ngroups = (p.K / BK) / (up2 ? 2 : 3);
-    if ((knob || up2) && p.rowhalo && batch == 1 && p.splits <= ngroups) {
-      halo = true;
-      const int TP = p.rowhalo == 2 ? 256 : 128;
-      if (p.rowhalo == 2) {
-        if (up2) kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 2, false, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 2, false, 2>;
-        else kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 2>;
-        threads = 512;
-      } else {
-        if (up2) kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true, 1, 1, 1, false, 2> : conv3_rowhalo_kernel<WNT, YT, false, 1, 1, 1, false, 2>;
-        else kern = p.pair ? conv3_rowhalo_kernel<WNT, YT, true> : conv3_rowhalo_kernel<WNT, YT, false>;
-      }
-      const int Wg = up2 ? p.W : p.Wo;
-      const int XP = (p.halo_lin || Wg > TP) ? (TP + 2 + 7) / 8 : ((TP / Wg) * (Wg + 2) + 7) / 8;
-      lds_bytes = (size_t)2 * BN * 128 + (size_t)2 * XP * 1024;
-      p.ks_q = ngroups / p.splits;  // K slices in (chunk, kernel row) groups
-      p.ks_r = ngroups % p.splits;
-    }
-  }
-  if (p.up == 2 && !halo) return crg_fail(ctx, -22, "conv2d: the sub-pixel upsample form runs on the row-halo kernel only (Cout > 32, bf16 output or split planes)");
-  {
-    const size_t cap = halo ? (size_t)(p.rowhalo == 2 ? 116 : 80) * 1024 : lds;
-    if (int rc = crg_set_dyn_lds(ctx, reinterpret_cast<const void*>(kern), cap, "gemm")) return rc;
-  }
-  dim3 grid(p.tile_count * p.splits, batch, 1);
-  constexpr int slot = !GLDS ? (CONV ? CRG_K_CONV_X3 : CRG_K_GEMM_X3)
-                             : (CONV ? (WNT == 5 ? CRG_K_CONV_W5 : WNT == 4 ? CRG_K_CONV_W4 : CRG_K_CONV_W1)
-                                     : (WNT == 5 ? CRG_K_GEMM_W5 : WNT == 4 ? CRG_K_GEMM_W4 : CRG_K_GEMM_W1));
-  crg_prof_scope ps(ctx, st, slot, wk.flops, wk.bytes);
-  {
-    crg_route& r = ctx->route;  // (the tail split launches twice: `launch` merges the two records)
-    r.kernel = halo ? CRG_ROUTE_ROWHALO : GLDS ? CRG_ROUTE_GLDS : CRG_ROUTE_GEMM_REG;
-    r.wnt = WNT;
-    r.config = !GLDS ? 0 : (KG == 2 ? 3 : WMT == 2 ? 4 : 1);
-    r.splits = p.splits;
-    r.rowhalo = halo ? p.rowhalo : 0;
-    r.halo_lin = halo ? p.halo_lin : 0;
-    r.pair = p.pair;
-    r.up2 = p.up == 2 ? 1 : 0;
-    r.mx = 0;
-    r.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
-  }
-  if constexpr (GLDS && CONV && STAGES == 2 && WMT == 4 && KG == 1 && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
-    if (halo && p.rowhalo == 2 && p.ring) {
-      // one statistics partial per 256-pixel tile and channel instead of eight (crg_groupnorm_pre then needs no finalise launch):
-      // paired epilogue, no K slices, tiles that do not straddle samples
-      if (p.gstat && p.gstat_tile_ok && p.pair && p.splits == 1 && (p.Ho * p.Wo) % 256 == 0) p.gstat_rows = 256;
-      ctx->route.kernel = CRG_ROUTE_CONV_PP;
-      ctx->route.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
-      return launch_conv_pp(ctx, st, p, WNT);
-    }
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(threads), lds_bytes, st, p);
-  CRG_CHECK_LAUNCH(ctx, "gemm");
-  return 0;
+  if (L.taps == 2) return L.pair ? conv3_rowhalo_kernel<WNT, bf16, true, 1, 1, 1, false, 2> : conv3_rowhalo_kernel<WNT, bf16, false, 1, 1, 1, false, 2>;
+  return L.pair ? conv3_rowhalo_kernel<WNT, bf16, true> : conv3_rowhalo_kernel<WNT, bf16, false>;
 }
 
-// Tile / pipeline configuration of the LDS-DMA kernel, by how many blocks the problem yields (256 CUs):
-//   A  128 x BN tile, 4 waves, 2-deep ring  : >= ~1.5 blocks per CU (after split-K); two blocks share a CU and hide each
-//                                             other's latencies
-//   D   64 x BN tile, 4 waves, 2-deep ring  : 192..1023 tiles of 128 rows (GEGLU epilogues: 192..383) and a short K: twice the blocks
-//                                             (4096x1280x1280: A 26.7, 8-wave 128-row variant 25.5, D 23.6 us).  Round 3, device time
-//                                             inside a captured graph (tools/lin_probe.py): 32768x320x320 + residual 25.8 (A) -> 22.4,
-//                                             8192x1920x640 41.6 -> 35.3, 2048x3840x1280 41.8 -> 34.6, 32768x320x1280 49.8 -> 45.3 us; the
-//                                             GEGLU GEMMs (128-wide tiles, heavy epilogue) keep A: 8192x5120x640 82 (A) vs 89 (D)
-//   C   64 x BN tile, 8 waves (two k-groups, folded through LDS), 4-deep ring : < 192 tiles (16x16 / 8x8 token GEMMs): one
-//                                             block per CU at most, so the waves and the ring depth come from inside the block
-//                                             (2048x1280x1280: A 24.7, C 16.7 us)
-template <int WNT, int NSPLIT, typename AT, typename YT, bool CONV>
-int launch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
-  constexpr int BN = 32 * WNT;
-  constexpr bool GLDS = (NSPLIT == 1) && (sizeof(AT) == 2);
-  p.zero_page = (const bf16*)ctx->zero_page;
-  p.tiles_n = (p.N + BN - 1) / BN;
-  static const int force = getenv("CRG_GEMM_CFG") ? atoi(getenv("CRG_GEMM_CFG")) : 0;  // dev knob: 1 = A, 3 = C, 4 = D
-  // split-K first, on 128-row tiles: a long K is the cheapest source of blocks.  Only problems that stay below ~1 block per
-  // CU after that (short K) change the tile / wave configuration.
-  p.tiles_m = (p.M + 127) / 128;
-  const bool inv = ctx->invariant > 0;  // batch-invariant mode: every size below is that of tune_samples samples (heur_blocks)
-  p.splits = choose_splits(p, heur_blocks(wk.heur, p, 128));
-  if constexpr (GLDS && !CONV && sizeof(YT) == 2) {
-    // persistent 256-row tiles (gemm_ring.hip) where every CU gets at least (almost) one: more FLOP per staged byte, no per-tile prologue
-    // (batch-invariant mode, a_is_weight: `batch` is the sample count, which ring_gemm_ok reads - dev knob CRG_GEMM_RING=2 only, since
-    // the default rule takes GEGLU GEMMs alone - so those calls stay on the kernel below whatever their batch)
-    if (!(inv && p.a_is_weight) && ring_gemm_ok(p, batch, ctx->n_cu, wk.heur.M)) {
-      if (ring_gemm_fits(p)) return launch_gemm_ring(ctx, st, p, wk.flops, wk.bytes);
-      // (mode off: the two-blocks-per-CU kernel takes what the descriptors cannot address.  Under the mode that would be a route picked by
-      // the size of the call)
-      if (inv) return crg_fail(ctx, -22, "gemm: batch-invariant mode routes this problem to the persistent 256-row kernel, whose 32-bit buffer descriptors cannot address M=%d rows: split the call", p.M);
-    }
-  }
-  int cfg = 1;
-  if (GLDS && p.splits == 1) {
-    const long blocks = heur_blocks(wk.heur, p, 128);
-    static const int d_max = getenv("CRG_GEMM_D_MAX") ? atoi(getenv("CRG_GEMM_D_MAX")) : 384;      // dev knob: 64-row tiles below this many 128-row tiles (plain epilogues)
-    static const int d_max_g = getenv("CRG_GEMM_D_MAXG") ? atoi(getenv("CRG_GEMM_D_MAXG")) : 384;  // ... GEGLU epilogues
-    static const int d_max_c1 = getenv("CRG_CONV1_D_MAX") ? atoi(getenv("CRG_CONV1_D_MAX")) : 384;   // ... 1x1 convs (virtual-concat skip convs)
-    // (3x3 convs keep 384: above it they run on the row-halo / ring kernels)
-    if (blocks < 192) cfg = 3;
-    else if (blocks < (CONV ? (p.ks == 1 ? d_max_c1 : d_max_g) : (p.epi == CRG_EPI_GEGLU ? d_max_g : d_max))) cfg = 4;
-  }
-  if (GLDS && force) cfg = force;
-  if (p.up == 2) cfg = 1;  // the sub-pixel upsample form exists on the row-halo kernel (configuration A's place) only
-  if (cfg == 3 || cfg == 4) {
-    p.tiles_m = (p.M + 63) / 64;
-    p.splits = force ? choose_splits(p, heur_blocks(wk.heur, p, 64)) : 1;
-  }
-  if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
-    // row-halo conv on 256-row tiles (one 8-wave block per CU): same K slices, half the m-tiles
-    static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 2;  // dev knob: 0 plain implicit GEMM, 1 128-row tiles only
-    const int ngroups = (p.K / BK) / (p.up == 2 ? 2 : 3);
-    const int Wg = p.up == 2 ? p.W : p.Wo;  // (sub-pixel form: source-grid geometry, tiles must not straddle a parity)
-    // (batch-invariant mode: whole tiles per SAMPLE, so that the form does not come and go with the parity of the sample count)
-    if (knob == 2 && cfg == 1 && p.rowhalo && batch == 1 && p.splits <= ngroups && (inv ? wk.heur.rps % 256 == 0 : p.M % 256 == 0) &&
-        (p.halo_lin || (Wg <= 256 ? 256 % Wg == 0 : Wg % 256 == 0)) && (p.up != 2 || (p.H * p.W) % 256 == 0)) {
-      // one block per CU: only when the grid fills its rounds of 256 blocks (a 288-block grid would run a second round 1/8 full)
-      const long blocks2 = heur_blocks(wk.heur, p, 256) * p.splits;
-      const long rounds = (blocks2 + 255) / 256;
-      if (blocks2 * 100 >= rounds * 256 * 85) {
-        p.rowhalo = 2;
-        p.tiles_m = p.M / 256;
-      }
-    }
-  }
-  p.ring = 0;
-  if constexpr (GLDS && CONV && sizeof(YT) == 2 && (WNT == 4 || WNT == 5)) {
-    // the staggered-wave kernel (conv_pp.hip) for the 256-row configuration, where its buffer descriptors can address the operands
-    if (p.rowhalo == 2 && p.up != 2 && p.w_bytes) {
-      const bool fits = p.a_bytes && (p.C2 == 0 || p.x2_bytes) && (long)p.M / (p.Ho * p.Wo) * p.H * p.W < (1 << 24);  // the only clause that reads the sample count
-      if (fits) p.ring = 1;
-      else if (inv) return crg_fail(ctx, -22, "conv2d: batch-invariant mode routes this conv to the staggered 256-pixel-tile kernel, whose buffer descriptors cannot address %d samples of %d x %d: split the call", p.M / (p.Ho * p.Wo), p.H, p.W);
-    }
-  }
-  if (p.splits > 1) {
-    const size_t bytes = (size_t)batch * p.splits * p.M * p.N * sizeof(float);
-    p.slab = (float*)crg_scratch(ctx, bytes);
-    if (!p.slab) return crg_fail(ctx, -12, "gemm: out of scratch for %d split-K slabs", p.splits);
-  }
-  choose_xcd_partition(p, wk);
-  p.tile_base = 0;
-  p.tile_count = p.tiles_n * p.tiles_m;
-  p.slab_row0 = 0;
-  int rc;
-  if constexpr (GLDS) {
-    // Tail split: with two blocks per CU a grid runs in rounds of 512 blocks; T = 512 k + r with a small r costs a whole extra
-    // round for r blocks (768x768 latents: 576 tiles -> the second round is 1/8 full and the conv runs at 56 % of its rate).
-    // The first 512 k tiles go out as they are; the last r tiles - whole rows of m-tiles - are cut along K so that they
-    // fill the chip once more for a fraction of a round, and are summed by the split-K reduce over just their rows.
-    const int T = p.tile_count, nk = (p.K + BK - 1) / BK;
-    const int r = T % 512, T1 = T - r;
-    // (not with a transposed column range: the K-split tail would have to emit V^T from the reduce pass - ADVICE r3)
-    // (off under the batch-invariant mode: which rows fall into the tail depends on the sample's position in the call)
-    if (!inv && cfg == 1 && p.rowhalo != 2 && p.splits == 1 && batch == 1 && T1 >= 512 && r > 0 && r <= 224 && nk >= 16 && r % p.tiles_n == 0 &&
-        p.epi != CRG_EPI_GEGLU && !(p.N & 3) && !p.vt && !p.rstat && !p.ln_stat) {
-      int s2 = 512 / r;
-      if (s2 > nk / 4) s2 = nk / 4;
-      if (s2 > 8) s2 = 8;
-      if (s2 >= 2) {
-        const int row0 = (T1 / p.tiles_n) * 128;
-        float* slab = (float*)crg_scratch(ctx, (size_t)s2 * (p.M - row0) * p.N * sizeof(float));
-        if (!slab) return crg_fail(ctx, -12, "gemm: out of scratch for the tail slab");
-        p.xg_s = 0;  // partial ranges use the contiguous-run order
-        p.tile_count = T1;
-        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * T1 / T, wk.bytes * T1 / T, 0, 0, wk.heur});
-        if (rc) return rc;
-        p.tile_base = T1;
-        p.tile_count = r;
-        p.splits = s2;
-        p.slab = slab;
-        p.slab_row0 = row0;
-        const int pair1 = ctx->route.pair;
-        rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, Work{wk.flops * r / T, wk.bytes * r / T, 0, 0, wk.heur});
-        if (rc) return rc;
-        ctx->route.splits = 1;  // the record describes the main launch; of the tail it keeps the K cut
-        ctx->route.pair = pair1;
-        ctx->route.tail_splits = s2;
-        return launch_reduce<YT>(ctx, st, p, 1);
-      }
-    }
-#ifndef CRG_C_STAGES  // dev knob (tools/build_one_variant.sh): ring depth of configuration C
-#define CRG_C_STAGES 4
-#endif
-    if (cfg == 3) rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, CRG_C_STAGES, 2, 2>(ctx, st, p, batch, wk);
-    else if (cfg == 4) rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 2, 1>(ctx, st, p, batch, wk);
-    else rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, wk);
-  } else {
-    rc = launch_kernel<WNT, NSPLIT, AT, YT, CONV, 2, 4, 1>(ctx, st, p, batch, wk);
-  }
-  if (rc) return rc;
-  if (p.splits > 1) return launch_reduce<YT>(ctx, st, p, batch);
-  return 0;
-}
-
-// fp32-class operands that arrive as pre-split bf16 planes: LDS-DMA kernel with NS = 2, 128 x BN tile, 8 waves in two
-// k-groups, 2-deep ring (4 planes x 2 stages fill the LDS: one block per CU, so the second wave per SIMD comes from the k-groups).
+// gemm_kernel<WNT, NSPLIT, AT, YT, CONV, NSPLIT>: fp32 A with the half-type product, or split-bf16 on 8 waves (two k-groups)
 template <int WNT, bool CONV>
-int launch_planes(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
-  constexpr int BN = 32 * WNT;
-  constexpr size_t lds = (size_t)2 * 2 * (128 + BN) * 128 + 1024;
-  p.zero_page = (const bf16*)ctx->zero_page;
-  if (p.gstat && (batch != 1 || (p.N & 3) || (p.M & 31) || (p.ldy & 3)))
-    return crg_fail(ctx, -22, "gemm/conv: GroupNorm statistics need an unbatched problem with N %% 4 == 0 and M %% 32 == 0");
-  p.tiles_n = (p.N + BN - 1) / BN;
-  p.tiles_m = (p.M + 127) / 128;
-  p.splits = p.gstat ? 1 : choose_splits(p, heur_blocks(wk.heur, p, 128));  // the statistics come out of the epilogue: no K split
-  if (p.splits > 1) {
-    p.slab = (float*)crg_scratch(ctx, (size_t)batch * p.splits * p.M * p.N * sizeof(float));
-    if (!p.slab) return crg_fail(ctx, -12, "gemm: out of scratch for %d split-K slabs", p.splits);
-  }
-  choose_xcd_partition(p, wk);
-  p.tile_base = 0;
-  p.tile_count = p.tiles_n * p.tiles_m;
-  p.slab_row0 = 0;
-  void (*kern)(GemmP) = gemm_glds_kernel<WNT, float, CONV, 2, 4, 2, 2>;
-  size_t lds_bytes = lds;
-  int units = (p.K + BK - 1) / BK;  // K slices in k-tiles ...
-  bool halo = false;
-  if constexpr (CONV && (WNT == 4 || WNT == 5)) {
-    static const int knob = getenv("CRG_ROWHALO") ? atoi(getenv("CRG_ROWHALO")) : 1;  // dev knob: 0 = plain implicit GEMM
-    const bool up2 = p.up == 2;  // sub-pixel form: groups of two k-tiles, geometry of the source grid, this kernel only (no knob)
-    const int ngroups = (p.K / BK) / (up2 ? 2 : 3);
-    if ((knob || up2) && p.rowhalo && batch == 1 && p.splits <= ngroups) {
-      halo = true;
-      kern = p.mx ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, true>
-                  : up2 ? conv3_rowhalo_kernel<WNT, float, false, 2, 2, 1, false, 2> : conv3_rowhalo_kernel<WNT, float, false, 2, 2>;
-      const int Wg = up2 ? p.W : p.Wo;
-      const int XP = (p.halo_lin || Wg > 128) ? 17 : ((128 / Wg) * (Wg + 2) + 7) / 8;
-      lds_bytes = (size_t)2 * 2 * BN * 128 + (size_t)2 * 2 * XP * 1024;
-      units = ngroups;  // ... or in (chunk, kernel row) groups
-    }
-  }
-  {
-    const size_t cap = halo ? (size_t)(2 * 2 * BN * 128 + 2 * 2 * 18 * 1024) : lds;  // eligible widths need <= 18 pieces per row buffer
-    if (int rc = crg_set_dyn_lds(ctx, reinterpret_cast<const void*>(kern), cap, "gemm(planes)")) return rc;
-  }
-  if (p.up == 2 && !halo) return crg_fail(ctx, -22, "conv2d: the sub-pixel upsample form runs on the row-halo kernel only (Cout > 32)");
-  if (p.mx && !halo) return crg_fail(ctx, -22, "conv2d: the MX form takes 3x3 / stride 1 / pad 1 convs with Cin %% 64 == 0 (the row-halo kernel's domain)");
-  {
-    p.ks_q = units / p.splits;
-    p.ks_r = units % p.splits;
-    p.pair = 0;
-    crg_prof_scope ps(ctx, st, CONV ? CRG_K_CONV_X3 : CRG_K_GEMM_X3, wk.flops, wk.bytes);
-    hipLaunchKernelGGL(kern, dim3(p.tiles_n * p.tiles_m * p.splits, batch, 1), dim3(512), lds_bytes, st, p);
-    CRG_CHECK_LAUNCH(ctx, "gemm(planes)");
-    crg_route& r = ctx->route;
-    r.kernel = CRG_ROUTE_PLANES;
-    r.wnt = WNT;
-    r.splits = p.splits;
-    r.rowhalo = halo ? 1 : 0;
-    r.halo_lin = halo ? p.halo_lin : 0;
-    r.up2 = p.up == 2 ? 1 : 0;
-    r.mx = p.mx ? 1 : 0;
-    r.gn_stats_rows = p.gstat ? p.gstat_rows : 0;
-  }
-  if (p.splits > 1) {
-    const long total4 = (long)p.M * (p.N >> 2);
-    const int rg = (int)((total4 + 255) / 256 > 2048 ? 2048 : (total4 + 255) / 256);
-    crg_prof_scope ps(ctx, st, CRG_K_SPLITK, (double)batch * p.splits * p.M * p.N, (double)batch * p.M * p.N * (4.0 * p.splits + 4));
-    hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(rg, batch), dim3(256), 0, st, p);
-    CRG_CHECK_LAUNCH(ctx, "splitk_reduce");
-    ctx->route.reduce = CRG_REDUCE_PLAIN;
-  }
-  return 0;
+KernFn pick_reg(const Launch& L) {
+  if (L.ns == 1) return L.y_f32 ? gemm_kernel<WNT, 1, float, float, CONV, 1> : gemm_kernel<WNT, 1, float, bf16, CONV, 1>;
+  if (L.a_f32) return gemm_kernel<WNT, 2, float, float, CONV, 2>;
+  if constexpr (!CONV) return gemm_kernel<WNT, 2, bf16, float, false, 2>;
+  return nullptr;
 }
 
-template <int NSPLIT, typename AT, typename YT, bool CONV>
-int launch_wnt(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, Work wk) {
-  // 160-wide tiles when they divide N (all UNet widths are multiples of 320), else 128-wide.
-  const bool geglu = p.epi == CRG_EPI_GEGLU;
-  if (!geglu && p.N <= 32) return launch<1, NSPLIT, AT, YT, CONV>(ctx, st, p, batch, wk);  // conv_out-like thin outputs
-  if (!geglu && p.N % 160 == 0) return launch<5, NSPLIT, AT, YT, CONV>(ctx, st, p, batch, wk);
-  return launch<4, NSPLIT, AT, YT, CONV>(ctx, st, p, batch, wk);
+template <int WNT, bool CONV>
+KernFn pick_family(const Launch& L) {
+  switch (L.family) {
+    case crg_plan::F_GEMM_REG: return pick_reg<WNT, CONV>(L);
+    case crg_plan::F_GLDS: return L.y_f32 ? pick_glds<WNT, float, CONV>(L) : pick_glds<WNT, bf16, CONV>(L);
+    case crg_plan::F_ROWHALO:
+      if constexpr (CONV && WNT != 1) return pick_rowhalo<WNT>(L);
+      return nullptr;
+    default: return nullptr;
+  }
 }
 
 template <bool CONV>
-int dispatch(crg_ctx* ctx, hipStream_t st, GemmP& p, int batch, int a_dtype, int y_dtype, int prec, Work wk) {
-  // GroupNorm statistics: the bf16 path (paired epilogue / split-K reduce), or the fp32-class conv on pre-split planes (its fp32 epilogue)
-  const bool gstat_bf16 = prec == CRG_PREC_BF16 && a_dtype == CRG_BF16 && y_dtype == CRG_BF16 && (p.N & 7) == 0;
-  const bool gstat_planes = (prec == CRG_PREC_BF16X3 || prec == CRG_PREC_F16MX) && a_dtype == CRG_BF16 && y_dtype == CRG_F32 && p.a_lo && !p.a_is_weight && (p.N & 3) == 0;
-  if (p.gstat && !((gstat_bf16 || gstat_planes) && batch == 1 && p.epi == CRG_EPI_NONE))
-    return crg_fail(ctx, -22, "gemm/conv: GroupNorm statistics need bf16 in / out (N %% 8 == 0) or pre-split planes in / fp32 out (N %% 4 == 0), batch 1 and a plain epilogue");
-  if (prec == CRG_PREC_BF16) {
-    if (a_dtype == CRG_BF16 && y_dtype == CRG_BF16) return launch_wnt<1, bf16, bf16, CONV>(ctx, st, p, batch, wk);
-    if (a_dtype == CRG_BF16 && y_dtype == CRG_F32) return launch_wnt<1, bf16, float, CONV>(ctx, st, p, batch, wk);
-    if (a_dtype == CRG_F32 && y_dtype == CRG_BF16) return launch_wnt<1, float, bf16, CONV>(ctx, st, p, batch, wk);
-    if (a_dtype == CRG_F32 && y_dtype == CRG_F32) return launch_wnt<1, float, float, CONV>(ctx, st, p, batch, wk);
-  } else if (prec == CRG_PREC_F16MX) {
-    if (CONV && p.mx && y_dtype == CRG_F32 && p.a_lo && p.w_lo && p.epi == CRG_EPI_NONE) {
-      if (p.N % 160 == 0) return launch_planes<5, CONV>(ctx, st, p, batch, wk);
-      return launch_planes<4, CONV>(ctx, st, p, batch, wk);
-    }
-  } else if (prec == CRG_PREC_BF16X3) {
-    if (a_dtype == CRG_BF16 && y_dtype == CRG_F32 && p.a_lo && !p.a_is_weight && p.epi == CRG_EPI_NONE) {
-      if (p.N <= 32) return launch_planes<1, CONV>(ctx, st, p, batch, wk);
-      if (p.N % 160 == 0) return launch_planes<5, CONV>(ctx, st, p, batch, wk);
-      return launch_planes<4, CONV>(ctx, st, p, batch, wk);
-    }
-    if (a_dtype == CRG_F32 && y_dtype == CRG_F32) return launch_wnt<2, float, float, CONV>(ctx, st, p, batch, wk);
-    if (!CONV && a_dtype == CRG_BF16 && y_dtype == CRG_F32 && p.a_is_weight)
-      return launch_wnt<2, bf16, float, false>(ctx, st, p, batch, wk);
+KernFn pick_kernel(const Launch& L) {
+  switch (L.wnt) {
+    case 1: return pick_family<1, CONV>(L);
+    case 4: return pick_family<4, CONV>(L);
+    case 5: return pick_family<5, CONV>(L);
+    default: return nullptr;
   }
-  return crg_fail(ctx, -22, "gemm/conv: unsupported dtype/precision combination a=%d y=%d prec=%d", a_dtype, y_dtype, prec);
 }
 
+template <bool CONV>
+int launch_one(crg_ctx* ctx, hipStream_t st, GemmP& p, const Launch& L, double flops, double bytes) {
+  p.splits = L.splits; p.ks_q = L.ks_q; p.ks_r = L.ks_r;
+  p.tile_base = L.tile_base; p.tile_count = L.tile_count; p.slab_row0 = L.slab_row0;
+  p.pair = L.pair;
+  const bool x3 = L.family == crg_plan::F_GEMM_REG || L.ns == 2;
+  const int slot = x3 ? (CONV ? CRG_K_CONV_X3 : CRG_K_GEMM_X3)
+                      : (CONV ? (L.wnt == 5 ? CRG_K_CONV_W5 : L.wnt == 4 ? CRG_K_CONV_W4 : CRG_K_CONV_W1)
+                              : (L.wnt == 5 ? CRG_K_GEMM_W5 : L.wnt == 4 ? CRG_K_GEMM_W4 : CRG_K_GEMM_W1));
+  if (L.family == crg_plan::F_CONV_PP) {
+    crg_prof_scope ps(ctx, st, slot, flops, bytes);
+    return launch_conv_pp(ctx, st, p, L.wnt);
+  }
+  // A null pointer means that planner and switch disagree.  The planner's invariants keep it unreachable: F_GLDS with ns == 2 and every
+  // F_ROWHALO with ns == 2 come from P_PLANES alone, whose y is fp32; F_ROWHALO only for convs on 128- / 160-wide tiles; F_GEMM_REG with
+  // ns == 2 and a 16-bit A only for GEMMs (a_is_weight); wnt is tile_wnt / wide_wnt's 1, 4 or 5.
+  const KernFn kern = pick_kernel<CONV>(L);
+  if (!kern) return crg_fail(ctx, -22, "gemm/conv: no kernel for the planned launch (family %d, tile width %d)", L.family, 32 * L.wnt);
+  if (int rc = crg_set_dyn_lds(ctx, reinterpret_cast<const void*>(kern), L.lds_cap, L.ns == 2 ? "gemm(planes)" : "gemm")) return rc;
+  crg_prof_scope ps(ctx, st, slot, flops, bytes);
+  hipLaunchKernelGGL(kern, dim3(L.grid_x, L.grid_y, 1), dim3(L.threads), L.lds, st, p);
+  CRG_CHECK_LAUNCH(ctx, L.ns == 2 ? "gemm(planes)" : "gemm");
+  return 0;
+}
+
+// the reduce launch behind a split-K launch (whole problem, or - tail split - the rows >= slab_row0)
+int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, const Plan& pl, int batch, bool y_f32) {
+  const long rows = p.M - p.slab_row0;
+  crg_prof_scope ps(ctx, st, CRG_K_SPLITK, (double)batch * p.splits * rows * p.N, (double)batch * rows * p.N * (4.0 * p.splits + (y_f32 ? 4 : 2)));
+  const dim3 grid(pl.reduce_gx, pl.reduce_gy);
+  KernFn kern = nullptr;
+  switch (pl.reduce) {
+    case CRG_REDUCE_GN:
+      switch (pl.reduce_vpt) {
+        case 1: kern = splitk_reduce_gn_kernel<1>; break;
+        case 2: kern = splitk_reduce_gn_kernel<2>; break;
+        case 3: kern = splitk_reduce_gn_kernel<3>; break;
+        case 4: kern = splitk_reduce_gn_kernel<4>; break;
+        case 5: kern = splitk_reduce_gn_kernel<5>; break;
+        case 6: kern = splitk_reduce_gn_kernel<6>; break;
+        default: kern = splitk_reduce_gn_kernel<8>; break;
+      }
+      break;
+    case CRG_REDUCE_ROWS: kern = splitk_reduce_rows_kernel; break;
+    case CRG_REDUCE_STATS: kern = y_f32 ? splitk_reduce_stats_kernel<float> : splitk_reduce_stats_kernel<bf16>; break;
+    default: kern = y_f32 ? splitk_reduce_kernel<float> : splitk_reduce_kernel<bf16>; break;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, p);
+  CRG_CHECK_LAUNCH(ctx, pl.reduce == CRG_REDUCE_GN ? "splitk_reduce_gn" : "splitk_reduce");
+  return 0;
+}
+
+// `flops`, `bytes`: algorithmic work of the call (profiler)
+template <bool CONV>
+int run_plan(crg_ctx* ctx, hipStream_t st, GemmP& p, const Plan& pl, int batch, bool y_f32, double flops, double bytes) {
+  if (pl.rc) return crg_fail(ctx, pl.rc, "%s", pl.msg);
+  p.zero_page = (const bf16*)ctx->zero_page;
+  p.tiles_n = pl.tiles_n; p.tiles_m = pl.tiles_m;
+  p.xg_m = pl.xg_m; p.xg_n = pl.xg_n; p.xg_s = pl.xg_s;
+  p.rowhalo = pl.rowhalo; p.ring = pl.ring; p.gstat_rows = pl.gstat_rows;
+  if (pl.main.family == crg_plan::F_GEMM_RING) {
+    if (int rc = launch_gemm_ring(ctx, st, p, pl.main.wnt, flops, bytes)) return rc;
+    ctx->route = pl.route;
+    return 0;
+  }
+  const bool tail = pl.tail.family != crg_plan::F_NONE;
+  float* slab = nullptr;
+  if (pl.scratch_bytes) {
+    slab = (float*)crg_scratch(ctx, pl.scratch_bytes);
+    if (!slab) return tail ? crg_fail(ctx, -12, "gemm: out of scratch for the tail slab") : crg_fail(ctx, -12, "gemm: out of scratch for %d split-K slabs", pl.main.splits);
+  }
+  p.slab = pl.main.splits > 1 ? slab : nullptr;
+  if (tail) {
+    const double T = pl.main.tile_count + pl.tail.tile_count;
+    if (int rc = launch_one<CONV>(ctx, st, p, pl.main, flops * pl.main.tile_count / T, bytes * pl.main.tile_count / T)) return rc;
+    p.slab = slab;
+    if (int rc = launch_one<CONV>(ctx, st, p, pl.tail, flops * pl.tail.tile_count / T, bytes * pl.tail.tile_count / T)) return rc;
+  } else if (int rc = launch_one<CONV>(ctx, st, p, pl.main, flops, bytes)) {
+    return rc;
+  }
+  if (pl.reduce != CRG_REDUCE_NONE)
+    if (int rc = launch_reduce(ctx, st, p, pl, batch, y_f32)) return rc;
+  ctx->route = pl.route;
+  return 0;
+}
+
+crg_plan::Env plan_env(const crg_ctx* ctx) { return crg_plan::Env{ctx->invariant, ctx->n_cu, dev_knobs()}; }
+
 }  // namespace
+
+namespace crg_mm {
+// The dev knobs of the GEMM / conv dispatcher (crg_plan::Knobs), read once per process: the one place that calls getenv.
+const crg_plan::Knobs& dev_knobs() {
+  static const crg_plan::Knobs knobs = [] {
+    crg_plan::Knobs k;
+    const auto read = [](const char* name, int& v) {
+      const char* s = getenv(name);
+      if (s) v = atoi(s);
+      return s != nullptr;
+    };
+    read("CRG_SPLIT_BLOCKS", k.split_blocks);
+    read("CRG_SPLIT_MAX", k.split_max);
+    read("CRG_GEMM_CFG", k.gemm_cfg);
+    read("CRG_GEMM_D_MAX", k.d_max);
+    read("CRG_GEMM_D_MAXG", k.d_max_g);
+    read("CRG_CONV1_D_MAX", k.d_max_c1);
+    k.rowhalo_set = read("CRG_ROWHALO", k.rowhalo);
+    read("CRG_GEMM_RING", k.gemm_ring);
+    read("CRG_GEMM_RING_MIN", k.gemm_ring_min);
+    read("CRG_GEMM_RING_SUPER", k.gemm_ring_super);
+    read("CRG_GEMM_RING_STAG", k.gemm_ring_stag);
+    return k;
+  }();
+  return knobs;
+}
+}  // namespace crg_mm
 
 extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
   if (!ctx || !a) return -22;
@@ -2004,7 +1715,7 @@ extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
   p.gstat_rows = 32;
   if (a->gn_stats) CRG_REQUIRE(ctx, ((uintptr_t)a->gn_stats & 15) == 0, "gemm: gn_stats must be 16-byte aligned");
   if (a->vt) {
-    const int bn_ = a->N % 160 == 0 ? 160 : 128;
+    const int bn_ = 32 * crg_plan::wide_wnt(a->N, false);
     CRG_REQUIRE(ctx, a->prec == CRG_PREC_BF16 && a->a_dtype == CRG_BF16 && a->y_dtype == CRG_BF16 && a->batch == 1 && a->epilogue == CRG_EPI_NONE &&
                          !a->residual && !a->gn_stats && (a->bias_mode == CRG_BIAS_COL || !a->bias),
                 "gemm: a transposed column range needs a plain bf16 GEMM (no batch / residual / activation / statistics)");
@@ -2028,17 +1739,10 @@ extern "C" int crg_gemm(crg_ctx* ctx, void* stream, const crg_gemm_args* a) {
                 "gemm: ln_stats needs ln_colsum, an even number of 2..16 partials per row and 16-byte aligned pointers");
     p.ln_stat = a->ln_stats; p.ln_parts = a->ln_parts; p.ln_s = a->ln_colsum; p.ln_eps = a->ln_eps;
   }
-  // what the size heuristics read (heur_blocks): the call itself, or - batch-invariant mode - tune_samples samples of the per-sample problem
-  // (a_is_weight, transposed outputs: the rows are the weight's, the samples lie along `batch`)
-  const int rps = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
-  if (ctx->invariant > 0 && !a->a_is_weight)
-    CRG_REQUIRE(ctx, a->M % rps == 0, "gemm: batch-invariant mode: M=%d is not a whole number of samples of rows_per_sample=%d rows", a->M, rps);
-  const Heur heur = heur_of(ctx, a->M, a->batch, rps, a->a_is_weight != 0);
   const double flops = 2.0 * a->M * (double)a->N * a->K * a->batch;
   const double bytes = ((double)a->M * a->K * crg_dtype_size(a->a_dtype) + (double)a->N * a->K * 2 +
                         (double)a->M * a->N * crg_dtype_size(a->y_dtype) * (a->residual ? 2 : 1)) * a->batch;
-  return dispatch<false>(ctx, (hipStream_t)stream, p, a->batch, a->a_dtype, a->y_dtype, a->prec,
-                         Work{flops, bytes, (double)a->M * a->K * crg_dtype_size(a->a_dtype), (double)a->N * a->K * 2, heur});
+  return run_plan<false>(ctx, (hipStream_t)stream, p, crg_plan::plan_gemm(*a, plan_env(ctx)), a->batch, a->y_dtype == CRG_F32, flops, bytes);
 }
 
 extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
@@ -2084,15 +1788,14 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   }
   GemmP p{};
   p.a = a->x; p.a_lo = a->x_lo; p.x2 = a->x2; p.C1 = a->C1; p.C2 = a->C2; p.Ctot = Ctot;
-  p.w = (const bf16*)a->w; p.w_lo = (const bf16*)a->w_lo; p.ldw = (long)a->ksize * a->ksize * Ctot; p.w_bs = 0;
+  p.w = (const bf16*)a->w; p.w_lo = (const bf16*)a->w_lo; p.ldw = crg_plan::conv_k(*a); p.w_bs = 0;
   p.bias = a->bias; p.bias_mode = a->bias ? CRG_BIAS_COL : CRG_BIAS_NONE;
   p.res = a->residual; p.ldr = a->Cout; p.r_bs = 0;
   p.y = a->y; p.ldy = a->Cout; p.y_bs = 0;
-  p.M = a->N * a->Ho * a->Wo; p.N = a->Cout; p.K = a->ksize * a->ksize * Ctot; p.epi = CRG_EPI_NONE;
-  p.cvec = a->cvec; p.cvec_rows = a->Ho * a->Wo; p.cvec_ld = a->cvec_ld ? a->cvec_ld : a->Cout;
+  p.M = crg_plan::conv_rows(*a); p.N = a->Cout; p.K = crg_plan::conv_k(*a); p.epi = CRG_EPI_NONE;
+  p.cvec = a->cvec; p.cvec_rows = a->Ho * a->Wo; p.cvec_ld = crg_plan::conv_cvec_ld(*a);
   p.H = a->H; p.W = a->W; p.Ho = a->Ho; p.Wo = a->Wo; p.ks = a->ksize; p.stride = a->stride;
   p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.up = a->upsample2x;
-  if (up2) p.ldw = p.K = 4 * Ctot;  // per parity: 2 x 2 taps; the four [Cout][4 Cin] slabs follow each other
   if (a->prec == CRG_PREC_F16MX) {
     // mx_log2 = {w hi8, w lo8, x hi8, x lo8}: each plane stores value * 2^s, the instruction's E8M0 scale undoes it (127 - s).
     // k-group 0 multiplies w lo8 by x hi8, k-group 1 w hi8 by x lo8.
@@ -2104,20 +1807,6 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   p.gstat_rows = 32;
   p.gstat_tile_ok = a->gn_stats != nullptr && a->gn_stats_rows != nullptr;
   if (a->gn_stats) CRG_REQUIRE(ctx, ((uintptr_t)a->gn_stats & 15) == 0 && (a->Ho * a->Wo) % 32 == 0, "conv2d: gn_stats must be 16-byte aligned and Ho * Wo a multiple of 32");
-  p.cm = (a->ksize == 3 && Ctot % 64 == 0) ? 1 : 0;  // must match crg_pack_weight's layout rule
-  p.rowhalo = (p.cm && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 && a->Ho == Hv && a->Wo == Wv &&
-               a->C1 % 8 == 0 && a->x_dtype == CRG_BF16 &&
-               ((a->y_dtype == CRG_BF16 && a->prec == CRG_PREC_BF16) || (a->y_dtype == CRG_F32 && (a->prec == CRG_PREC_BF16X3 || a->prec == CRG_PREC_F16MX) && a->x_lo)))
-                  ? 1 : 0;
-  p.halo_lin = (a->Wo >= 16 && (a->Wo <= 128 ? 128 % a->Wo == 0 : a->Wo % 128 == 0)) ? 0 : 1;  // geometry of the output grid
-  if (up2) p.halo_lin = 0;  // (geometry of the source grid: checked above)
-  {
-    const double ab = (double)a->N * a->H * a->W * a->C1 * 2.0, xb = (double)a->N * a->H * a->W * a->C2 * 2.0, wb = (double)p.N * p.K * 2.0;
-    const double lim = 2147483648.0;
-    p.a_bytes = ab < lim ? (unsigned)ab : 0;
-    p.x2_bytes = xb < lim ? (unsigned)xb : 0;
-    p.w_bytes = wb < lim ? (unsigned)wb : 0;
-  }
   if (a->gn_y) {
     CRG_REQUIRE(ctx, a->gn_gamma && a->gn_beta && a->gn_groups > 0 && a->Cout % a->gn_groups == 0 && a->y,
                 "conv2d: the fused GroupNorm needs gamma, beta, a group count that divides Cout=%d and the raw output y", a->Cout);
@@ -2129,12 +1818,12 @@ extern "C" int crg_conv2d(crg_ctx* ctx, void* stream, const crg_conv_args* a) {
   const double flops = 2.0 * p.M * (double)p.N * p.K;
   const double bytes = (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype) + wbytes +
                        (double)p.M * p.N * crg_dtype_size(a->y_dtype) * (a->residual ? 2 : 1);
-  ctx->gn_fused = false;
-  const Heur heur = heur_of(ctx, p.M, 1, a->Ho * a->Wo, false);  // batch-invariant mode: tune_samples samples of Ho x Wo rows
-  const int rc = dispatch<true>(ctx, (hipStream_t)stream, p, 1, a->x_dtype, a->y_dtype, a->prec,
-                                Work{flops, bytes, (double)a->N * a->H * a->W * Ctot * crg_dtype_size(a->x_dtype), wbytes, heur});
-  if (a->gn_stats_rows) *a->gn_stats_rows = p.gstat_rows;
-  if (rc || !a->gn_y || ctx->gn_fused) return rc;
+  const Plan pl = crg_plan::plan_conv(*a, plan_env(ctx));
+  p.cm = pl.cm; p.halo_lin = pl.halo_lin;  // (K order, row-buffer form and the descriptor sizes: planner rules, plan_conv)
+  p.a_bytes = pl.a_bytes; p.x2_bytes = pl.x2_bytes; p.w_bytes = pl.w_bytes;
+  const int rc = run_plan<true>(ctx, (hipStream_t)stream, p, pl, 1, a->y_dtype == CRG_F32, flops, bytes);
+  if (a->gn_stats_rows) *a->gn_stats_rows = pl.gstat_rows;
+  if (rc || !a->gn_y || pl.gn_fused) return rc;
   // not split along K (or a shape the fused kernel does not take): the GroupNorm runs as its own launch(es) on the finished y
   return crg_groupnorm(ctx, stream, a->y, nullptr, a->Cout, a->gn_gamma, a->gn_beta, a->gn_y, a->N, a->Ho * a->Wo, a->Cout, a->gn_groups,
                        a->gn_eps, a->gn_silu, a->y_dtype);

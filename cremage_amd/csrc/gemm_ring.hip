@@ -16,9 +16,8 @@
 //     (out-of-range lanes are dropped), so that the number of vector-memory instructions a wave issues per tile is a compile-time
 //     constant - that is what lets the first two waits of a tile leave the previous tile's stores in flight.
 // Same MFMA layout as the other kernels (weights = A operand: a lane owns 4 (paired: 8) consecutive output channels of one row).
-// Launched from gemm_conv.hip's `launch` where it measured faster than the two-blocks-per-CU kernel (see ring_gemm_ok below).
+// Launched from gemm_conv.hip's `run_plan` where it measured faster than the two-blocks-per-CU kernel (gemm_plan.h: ring_gemm_ok).
 #include "gemm_shared.h"
-#include <stdlib.h>
 
 namespace crg_mm {
 
@@ -459,45 +458,9 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// Shapes the ring kernel takes in place of gemm_glds_kernel: bf16 in / out, one problem (no batch), K a multiple of 64, plain or
-// GEGLU epilogue (no SiLU, no per-row bias, no timestep vector, no GroupNorm statistics), every extent addressable through a 32-bit
-// buffer descriptor - and, by measurement (tools/lin_probe.py / lin_probe_xl.py, device time inside a captured graph, round 3):
-//   GEGLU epilogue, >= 3 tiles per CU : 8192 x 5120 x 640   82 -> 71 us,  16384 x 5120 x 640  164 -> 145 us,  4096 x 10240 x 1280  139 -> 127 us
-//   GEGLU, 2.5 tiles per CU           : 2048 x 10240 x 1280  69 -> 69 us (equal)
-//   plain epilogue (any tile count)   : 32768 x 320 x 320 + residual 18.6 -> 21.9 us, 8192 x 1920 x 640 30.5 -> 34.4 us, 32768 x 320 x 1280 36 -> 40 us,
-//                                       16384 x 1920 x 640 58.5 -> 57 us: the two-blocks-per-CU kernel hides its short epilogue behind the
-//                                       other block's MFMAs already; this kernel's 52 one-KiB DMA pieces per k-tile (the row-halo conv needs
-//                                       32) then cost more issue time than the larger tile saves
-// so it is routed for GEGLU GEMMs with at least three 256-row tiles per CU.  CRG_GEMM_RING: 0 = never, 1 (default) = that rule,
-// 2 = plain epilogues as well (from CRG_GEMM_RING_MIN percent of a tile per CU, default 300).
-// `heur_M`: the rows the tile count is taken from (the call's own, or those of tune_samples samples under the batch-invariant mode: the
-// kernel is then also launched on fewer tiles than CUs - grid = tile count, one tile per block, every block non-empty).
-bool ring_gemm_ok(const GemmP& p, int batch, int n_cu, long heur_M) {
-  static const int on = getenv("CRG_GEMM_RING") ? atoi(getenv("CRG_GEMM_RING")) : 1;
-  static const int min_pct = getenv("CRG_GEMM_RING_MIN") ? atoi(getenv("CRG_GEMM_RING_MIN")) : 300;  // dev knob: least tiles, % of the CU count
-  if (!on || batch != 1 || p.K % 64 || p.K < 128 || p.splits != 1) return false;
-  if (p.epi != CRG_EPI_GEGLU && !(on >= 2 && p.epi == CRG_EPI_NONE)) return false;
-  if (p.bias_mode == CRG_BIAS_ROW || p.cvec || p.gstat || p.vt || p.rstat) return false;
-  if (p.ln_stat && (p.res || ((uintptr_t)p.ln_s & 15))) return false;
-  const bool geglu = p.epi == CRG_EPI_GEGLU;
-  if (geglu ? (p.N % 32 || (p.ldy & 3)) : (p.N % 8 || (p.ldy & 7) || ((uintptr_t)p.y & 15))) return false;
-  if (p.res && ((p.ldr & 7) || ((uintptr_t)p.res & 15))) return false;
-  if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-  if ((double)p.N * p.ldw * 2 >= 2147483648.0) return false;
-  const int bn = (!geglu && p.N % 160 == 0) ? 160 : 128;
-  const long tiles = ((heur_M + 255) / 256) * ((p.N + bn - 1) / bn);
-  return tiles * 100 >= (long)(n_cu > 0 ? n_cu : 256) * min_pct;
-}
-
-// every extent that grows with the rows of the CALL addressable through a 32-bit buffer descriptor
-bool ring_gemm_fits(const GemmP& p) {
-  const double lim = 2147483648.0;
-  return !((double)p.M * p.lda * 2 >= lim || (double)p.M * p.ldy * 2 >= lim || (p.res && (double)p.M * p.ldr * 2 >= lim));
-}
-
-int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops, double bytes) {
+// Which shapes run here is the planner's rule (gemm_plan.h: ring_gemm_ok / ring_gemm_fits), and so is the tile width `wnt`.
+int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, int wnt, double flops, double bytes) {
   const bool geglu = g.epi == CRG_EPI_GEGLU;
-  const int wnt = (!geglu && g.N % 160 == 0) ? 5 : 4;
   const int bn = 32 * wnt;
   RingP p{};
   p.a = (const bf16*)g.a; p.lda = g.lda; p.a_bytes = (unsigned)((double)g.M * g.lda * 2);
@@ -530,7 +493,7 @@ int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops,
   if (grid > p.tile_count) grid = p.tile_count;
   p.st_m = p.st_n = 0;
   {
-    static const int super = getenv("CRG_GEMM_RING_SUPER") ? atoi(getenv("CRG_GEMM_RING_SUPER")) : 1;  // dev knob (A/B): 0 = n-fastest tile order inside an XCD's share
+    const int super = dev_knobs().gemm_ring_super;  // dev knob (A/B): 0 = n-fastest tile order inside an XCD's share
     const int per = grid / 8;  // blocks of one XCD, i.e. tiles it works on at a time
     if (super && p.xg_m && grid % 8 == 0 && per > 0) {
       const int nnl = p.tiles_n / p.xg_n, nml = p.tiles_m / p.xg_m;
@@ -547,7 +510,7 @@ int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops,
       }
     }
   }
-  static const int stag = getenv("CRG_GEMM_RING_STAG") ? atoi(getenv("CRG_GEMM_RING_STAG")) : 1;  // dev knob: 0 = all eight waves in lockstep (round 3a)
+  const int stag = dev_knobs().gemm_ring_stag;  // dev knob: 0 = all eight waves in lockstep (round 3a)
   void (*kern)(RingP) = stag ? (geglu ? gemm_ring_kernel<4, true> : (wnt == 5 ? gemm_ring_kernel<5, false> : gemm_ring_kernel<4, false>))
                              : (geglu ? gemm_ring_kernel<4, true, false> : (wnt == 5 ? gemm_ring_kernel<5, false, false> : gemm_ring_kernel<4, false, false>));
   if (g.ln_stat)  // LayerNorm epilogue: staggered schedule only
@@ -557,9 +520,6 @@ int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& g, double flops,
   crg_prof_scope ps(ctx, st, wnt == 5 ? CRG_K_GEMM_W5 : CRG_K_GEMM_W4, flops, bytes);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, p);
   CRG_CHECK_LAUNCH(ctx, "gemm_ring");
-  ctx->route.kernel = CRG_ROUTE_GEMM_RING;
-  ctx->route.wnt = wnt;
-  ctx->route.splits = 1;
   return 0;
 }
 

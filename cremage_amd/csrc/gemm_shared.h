@@ -2,6 +2,7 @@
 // block -> tile mapping, LDS swizzle, epilogues, counted vmcnt wait.
 #pragma once
 #include "crg_common.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 namespace crg_mm {
@@ -63,6 +64,7 @@ struct GemmP {
 
 constexpr int BM = 128;
 constexpr int BK = 64;
+static_assert(BM == 128 && BK == crg_plan::BK, "the planner (gemm_plan.h) counts 128-row tiles and k-tiles of crg_plan::BK");
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Block -> (m-tile, n-tile, k-slice).  The dispatcher deals workgroups round-robin to the 8 XCDs (block L runs on XCD
@@ -571,9 +573,10 @@ __device__ __forceinline__ void wait_vmcnt() {  // s_waitcnt vmcnt(N) only (expc
 // conv_pp.hip: 3x3 / stride 1 conv on 256-pixel tiles, 4-slot weight ring + halo'd row buffers, the two waves of a SIMD half a k-tile
 // apart (bf16), launched in place of conv3_rowhalo_kernel<.., MT = 2>
 int launch_conv_pp(crg_ctx* ctx, hipStream_t st, const GemmP& p, int wnt);
-// gemm_ring.hip: persistent 256-row-tile GEMM (bf16, plain / GEGLU epilogue), launched in place of gemm_glds_kernel where it applies
-bool ring_gemm_ok(const GemmP& p, int batch, int n_cu, long heur_M);
-bool ring_gemm_fits(const GemmP& p);
-int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& p, double flops, double bytes);
+// gemm_ring.hip: persistent 256-row-tile GEMM (bf16, plain / GEGLU epilogue), launched in place of gemm_glds_kernel where the planner
+// routes it (gemm_plan.h: ring_gemm_ok / ring_gemm_fits); wnt: the planner's tile width
+int launch_gemm_ring(crg_ctx* ctx, hipStream_t st, const GemmP& p, int wnt, double flops, double bytes);
+// gemm_conv.hip: the dev knobs of the dispatcher, read from the environment once
+const crg_plan::Knobs& dev_knobs();
 
 }  // namespace crg_mm

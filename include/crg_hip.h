@@ -306,7 +306,7 @@ enum crg_route_kernel {
   CRG_ROUTE_CONV_PP = 3,    /* conv3_pp_kernel (conv_pp.hip): the staggered 256-pixel-tile 3x3 conv                                    */
   CRG_ROUTE_GEMM_RING = 4,  /* gemm_ring_kernel (gemm_ring.hip): persistent 256-row tiles                                              */
   CRG_ROUTE_GEMM_REG = 5,   /* gemm_kernel: register-staged operands (fp32 A, or fp32-class on unsplit operands)                       */
-  CRG_ROUTE_PLANES = 6      /* launch_planes: fp32-class / MX on pre-split planes (gemm_glds_kernel or conv3_rowhalo_kernel, see rowhalo) */
+  CRG_ROUTE_PLANES = 6      /* fp32-class / MX on pre-split planes (gemm_glds_kernel<.., NS = 2> or conv3_rowhalo_kernel, see rowhalo)      */
 };
 enum crg_route_reduce {
   CRG_REDUCE_NONE = 0,
