@@ -14,8 +14,12 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libcrg_hip.so")
 LIB_F16 = os.path.join(HERE, "libcrg_hip_f16.so")  # the same sources with -DCRG_F16_BUILD: fp16 operands (crg_common.h)
-SOURCES = ["crg_api.hip", "gemm_conv.hip", "conv_pp.hip", "gemm_ring.hip", "lngemm.hip", "norms.hip", "attention.hip", "small_ops.hip", "poisson.hip", "blur_blend.hip", "mx8.hip", "attention_x3.hip", "video.hip"]
-HEADERS = [os.path.join(CSRC, "crg_common.h"), os.path.join(CSRC, "gemm_shared.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(HERE, "..", "include", "crg_hip.h")]
+# the long-compiling units first: the pool starts its jobs in this order
+SOURCES = ["gemm_glds_gemm.hip", "gemm_glds_conv.hip", "conv_rowhalo.hip", "video.hip", "attention.hip", "conv_pp.hip", "small_ops.hip",
+           "gemm_ring.hip", "lngemm.hip", "splitk_reduce.hip", "gemm_conv.hip", "crg_api.hip", "norms.hip", "poisson.hip", "blur_blend.hip", "mx8.hip",
+           "attention_x3.hip"]
+# every header an object may depend on: a change to any of them rebuilds everything (found by listing, so that none can be missing)
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(HERE, "..", "include", "crg_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 # attention.hip: without NaN-honouring semantics fmaxf lowers to plain v_max_f32 / v_max3_f32 instead of a canonicalising
 # v_max per MFMA output (32 extra VALU per 64-key tile in a VALU-bound loop).  Infinities (the -inf key mask) are kept.

@@ -20,11 +20,12 @@
 //
 // LDS: K tile [64][KS*16] with rows padded to 16*(2KS+1) bytes, V^T tile [NV*32][64] with rows padded
 // to 136 bytes: both fragment read patterns are bank-conflict free (guide §2 bank rules).
-#include "crg_common.h"
+#include "buf_access.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
+using namespace crg_buf;
 
 struct AttnP {
   const bf16* q; const bf16* k; const bf16* vt; bf16* o;
@@ -625,15 +626,6 @@ static __device__ __forceinline__ float attn_max_halves(float v) {
   return v;
 #endif
 }
-typedef __attribute__((address_space(3))) void* lptr_t;
-static __device__ __forceinline__ void attn_dma16(const void* base, unsigned bytes, char* lds, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds, 16, voff, soff, 0, 0);
-#endif
-}
-static __device__ __forceinline__ void attn_wait_vm0() { __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8)); }
-
 template <int KC>
 struct AttnKSwz {  // XOR span (chunks) and the per-row swizzle of the K image
   static constexpr int SPAN = KC % 2 == 1 ? 1 : (KC % 4 == 2 ? 2 : (KC % 8 == 4 ? 4 : (KC % 16 == 8 ? 8 : 16)));
@@ -707,8 +699,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_dma_kernel(AttnP p, unsigne
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int j = wave + NW * q;  // wave-uniform
-        if (j < KI) attn_dma16(K, k_bytes, Ks + j * 1024, voff[q], tile * 64 * (int)p.ldk * 2);
-        else if (j < NI) attn_dma16(VT, v_bytes, Ks + KBYTES + (j - KI) * 1024, voff[q], tile * 128);
+        if (j < KI) buf_dma16(K, k_bytes, Ks + j * 1024, voff[q], tile * 64 * (int)p.ldk * 2);
+        else if (j < NI) buf_dma16(VT, v_bytes, Ks + KBYTES + (j - KI) * 1024, voff[q], tile * 128);
       }
     }
   };
@@ -757,7 +749,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_dma_kernel(AttnP p, unsigne
   const unsigned long long mt0 = __builtin_amdgcn_s_memtime(), rt0 = tl;
 #endif
   issue(0, 0);
-  attn_wait_vm0();
+  wait_vmcnt0();
   __syncthreads();
   for (int super = 0; super < nsuper; ++super) {
     LAP(4);
@@ -886,7 +878,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_dma_kernel(AttnP p, unsigne
       }
       LAP(3);
     }
-    attn_wait_vm0();  // this wave's pieces of the next stage have landed (issued a whole stage ago)
+    wait_vmcnt0();  // this wave's pieces of the next stage have landed (issued a whole stage ago)
     __syncthreads();  // ... everyone's have, and everyone is done reading this stage
   }
 #ifdef CRG_ATTN_LAPS
@@ -1011,9 +1003,9 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_sp_kernel(AttnP p, unsigned
     for (int q = 0; q < NQ; ++q) {
       const int j = wave + NW * q;  // wave-uniform
       if (j < KC) {
-        if (kt >= 0) attn_dma16(K, k_bytes, smem + (kt & 1) * KBYTES + j * 1024, voff[q], kt * 64 * (int)p.ldk * 2);
+        if (kt >= 0) buf_dma16(K, k_bytes, smem + (kt & 1) * KBYTES + j * 1024, voff[q], kt * 64 * (int)p.ldk * 2);
       } else if (j < NI) {
-        if (vt >= 0) attn_dma16(VT, v_bytes, smem + 2 * KBYTES + (vt & 1) * VBYTES + (j - KC) * 1024, voff[q], vt * 128);
+        if (vt >= 0) buf_dma16(VT, v_bytes, smem + 2 * KBYTES + (vt & 1) * VBYTES + (j - KC) * 1024, voff[q], vt * 128);
       }
     }
   };
@@ -1093,7 +1085,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_sp_kernel(AttnP p, unsigned
     }
   };
   auto tile_end = [&]() {
-    attn_wait_vm0();
+    wait_vmcnt0();
     __syncthreads();
   };
   // Iteration tt (parity C = tt & 1), hand-placed: every fragment of the iteration is read first (the stages became valid at the

@@ -1,7 +1,7 @@
 // 3x3 / stride 1 / pad 1 conv on 256-pixel tiles with the two waves of every SIMD out of step (gfx950).
 //
 // (Round 2's conv3_ring_kernel - the same tile, LDS images and DMA pieces with all eight waves in lockstep - was removed in round 4.)
-// Same math, operand layout and row-halo staging as conv3_rowhalo_kernel<.., MT = 2> (gemm_conv.hip); the pipeline:
+// Same math, operand layout and row-halo staging as conv3_rowhalo_kernel<.., MT = 2> (conv_rowhalo.hip); the pipeline:
 //   * the weight ring has FOUR slots: W(t + 3) is issued in k-tile t and only has to be in LDS at the top of k-tile t + 2;
 //   * the row buffer of group g + 1 (R x (W + 2) pixels of one 64-channel chunk and kernel row, shared by the three taps kw = 0..2) is
 //     issued whole in the first k-tile of group g (its slot was last read in group g - 1);
@@ -25,8 +25,6 @@ namespace crg_mm {
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 __device__ __forceinline__ void pp_wait_vm_n(int n) {  // wave-uniform n: s_waitcnt vmcnt(n), n <= 12
   switch (n) {
     case 0: wait_vmcnt<0>(); break;
@@ -43,14 +41,6 @@ __device__ __forceinline__ void pp_wait_vm_n(int n) {  // wave-uniform n: s_wait
     case 11: wait_vmcnt<11>(); break;
     default: wait_vmcnt<12>(); break;
   }
-}
-
-// One LDS-DMA piece through a raw buffer descriptor: lane -> 16 bytes at base + voff + soff, zeros when out of [0, bytes).
-__device__ __forceinline__ void pp_dma16(const void* base, unsigned bytes, char* lds, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds, 16, voff, soff, 0, 0);
-#endif
 }
 
 #define PP_BARRIER()                       \
@@ -180,15 +170,15 @@ __global__ __launch_bounds__(512, 2) void conv3_pp_kernel(GemmP p) {
       int px = xp0[i] + r.drow;
       if (r.mid) px += (xmask[i] & 8u) ? p.W : 0;
       const int vo = (xmask[i] & r.bit) ? px * r.Cs2 + clog * 16 : OOB;
-      pp_dma16(r.base, r.bytes, r.xb + jp * 1024, vo, r.soff);
+      buf_dma16(r.base, r.bytes, r.xb + jp * 1024, vo, r.soff);
     }
   };
   auto w_piece = [&](int q, int tt) {  // piece q of this slice's weight k-tile tt into its ring slot
     if ((wave + NW * q) < WRG)
 #ifdef CRG_ABL_DMAHOT
-      pp_dma16(p.w, p.w_bytes, wring + (tt & 3) * WS_BYTES + (wave + NW * q) * 1024, wvo[q], (3 * g_begin) * 128);
+      buf_dma16(p.w, p.w_bytes, wring + (tt & 3) * WS_BYTES + (wave + NW * q) * 1024, wvo[q], (3 * g_begin) * 128);
 #else
-      pp_dma16(p.w, p.w_bytes, wring + (tt & 3) * WS_BYTES + (wave + NW * q) * 1024, wvo[q], (3 * g_begin + tt) * 128);
+      buf_dma16(p.w, p.w_bytes, wring + (tt & 3) * WS_BYTES + (wave + NW * q) * 1024, wvo[q], (3 * g_begin + tt) * 128);
 #endif
   };
 

@@ -159,7 +159,7 @@ __global__ void pack_kernel(const ST* __restrict__ src, bf16* __restrict__ hi, b
     long s;
     if (kind == CRG_PACK_CONV) {
       int tap, ci;
-      if (ks == 3 && n_in % 64 == 0) {  // chunk-major K: [Cin/64][tap][64] (see GemmP::cm in gemm_conv.hip)
+      if (ks == 3 && n_in % 64 == 0) {  // chunk-major K: [Cin/64][tap][64] (see GemmP::cm in gemm_shared.h)
         const int taps = ks * ks;
         const int chunk = k / (taps * 64), r = k - chunk * taps * 64;
         tap = r / 64;

@@ -2,10 +2,10 @@
 // and a small environment - tile width, configuration A / C / D, split-K factor, tail split, row-halo form, the staggered 256-pixel
 // kernel, the persistent ring GEMM, paired epilogue, XCD partition, the reduce kernel that follows and the GroupNorm statistics
 // granularity.  Host only, plain C++17: no HIP include, no GemmP, no crg_ctx, no getenv.  Pointers are read for null-ness and 16-byte
-// alignment, never dereferenced.  gemm_conv.hip (the launcher) fills GemmP from the args and the plan, picks the kernel pointer from the
-// plan's selectors and launches; tools/plan_dump.cpp runs the same functions without a device (tests/test_gemm_plan_cpu.py).
+// alignment, never dereferenced.  gemm_conv.hip (the launcher) fills GemmP from the args and the plan, asks the planned family's
+// picker (one per kernel file, gemm_shared.h) for the kernel pointer and launches; tools/plan_dump.cpp runs the same functions without a device (tests/test_gemm_plan_cpu.py).
 //
-// A new route: a rule here, a case in the launcher's switch of that kernel family, rows in tests/routes/ (DESIGN.md section 4).
+// A new route: a rule here, a case in that kernel family's picker (pick_* in the family's own file), rows in tests/routes/ (DESIGN.md section 4).
 #pragma once
 #include <stdarg.h>
 #include <stdint.h>

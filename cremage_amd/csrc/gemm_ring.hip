@@ -21,53 +21,11 @@
 
 namespace crg_mm {
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-static __device__ __forceinline__ void rg_dma16(const void* base, unsigned bytes, char* lds, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds, 16, voff, soff, 0, 0);
+#ifdef CRG_RG_ABL_NOSTORE  // timing ablation only: every 8-byte epilogue store goes out of range (buf_store8<true>)
+constexpr bool RG_DROP8 = true;
+#else
+constexpr bool RG_DROP8 = false;
 #endif
-}
-static __device__ __forceinline__ void rg_store16(void* base, unsigned bytes, int voff, const bf16x8& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
-  u32x4 r;
-  __builtin_memcpy(&r, &v, 16);
-  __builtin_amdgcn_raw_buffer_store_b128(r, rs, voff, 0, 0);
-#endif
-}
-static __device__ __forceinline__ void rg_store8(void* base, unsigned bytes, int voff, const bf16x4& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
-  u32x2 r;
-  __builtin_memcpy(&r, &v, 8);
-#ifdef CRG_RG_ABL_NOSTORE  // timing ablation only: the store goes out of range (dropped by the range check, still issued and counted)
-  voff = (int)0x80000000;
-#endif
-  __builtin_amdgcn_raw_buffer_store_b64(r, rs, voff, 0, 0);
-#endif
-}
-static __device__ __forceinline__ bf16x8 rg_load16(const void* base, unsigned bytes, int voff) {
-  bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-  __builtin_memcpy(&v, &r, 16);
-#endif
-  return v;
-}
-static __device__ __forceinline__ bf16x4 rg_load8(const void* base, unsigned bytes, int voff) {
-  bf16x4 v = {0, 0, 0, 0};
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
-  __builtin_memcpy(&v, &r, 8);
-#endif
-  return v;
-}
 static __device__ __forceinline__ void rg_wait(int n) {  // wave-uniform s_waitcnt vmcnt(n)
   switch (n) {
     case 0: wait_vmcnt<0>(); break;
@@ -214,10 +172,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
     char* ws = as + AS_BYTES;
     const int soff = is_kt * 128;
 #pragma unroll
-    for (int q = 0; q < AL; ++q) rg_dma16(p.a, p.a_bytes, as + (wave + NW * q) * 1024, a_vo[q], soff);
+    for (int q = 0; q < AL; ++q) buf_dma16(p.a, p.a_bytes, as + (wave + NW * q) * 1024, a_vo[q], soff);
 #pragma unroll
     for (int q = 0; q < WL; ++q)
-      if ((wave + NW * q) < WRG) rg_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, w_vo[q], soff);
+      if ((wave + NW * q) < WRG) buf_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, w_vo[q], soff);
     if (++is_kt == p.nk) {
       is_kt = 0;
       ++is_i;
@@ -316,7 +274,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
           bf16x4 o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16)(v[e] * crg_gelu_erf_f(g[e]));
-          rg_store8(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + jn) * 2) : OOB, o);
+          buf_store8<RG_DROP8>(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + jn) * 2) : OOB, o);
         }
       }
     } else {
@@ -336,7 +294,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
           const int m = m0 + wm * 64 + j * 16 + frow;
           f32x4 a4 = lncorr(acc[2 * u2][j], j, sa) + ba, b4 = lncorr(acc[2 * u2 + 1][j], j, sb) + bb;
           if (p.res) {
-            const bf16x8 r8 = rg_load16(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOB);
+            const bf16x8 r8 = buf_load16(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOB);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               a4[e] += (float)r8[e];
@@ -349,7 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
             o[e] = (bf16)a4[e];
             o[4 + e] = (bf16)b4[e];
           }
-          rg_store16(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOB, o);
+          buf_store16(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOB, o);
         }
       }
       if constexpr (WNT & 1) {
@@ -363,14 +321,14 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
           const int m = m0 + wm * 64 + j * 16 + frow;
           f32x4 a4 = lncorr(acc[WNT - 1][j], j, sa) + ba;
           if (p.res) {
-            const bf16x4 r4 = rg_load8(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOB);
+            const bf16x4 r4 = buf_load8(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOB);
 #pragma unroll
             for (int e = 0; e < 4; ++e) a4[e] += (float)r4[e];
           }
           bf16x4 o;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o[e] = (bf16)a4[e];
-          rg_store8(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOB, o);
+          buf_store8<RG_DROP8>(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOB, o);
         }
       }
     }
@@ -446,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ring_kernel(RingP p) {
         }
         __builtin_amdgcn_sched_barrier(0);
         reads(u);
-        __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the reads have returned before the next barrier lets the slot be refilled
+        wait_lgkmcnt0();  // the reads have returned before the next barrier lets the slot be refilled
       }
     }
     if (my_tiles > 0) {

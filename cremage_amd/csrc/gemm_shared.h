@@ -1,11 +1,13 @@
-// Shared pieces of the MFMA GEMM / implicit-GEMM conv kernels (gemm_conv.hip, conv_pp.hip, gemm_ring.hip): problem descriptor,
-// block -> tile mapping, LDS swizzle, epilogues, counted vmcnt wait.
+// Shared pieces of the MFMA GEMM / implicit-GEMM conv kernels (gemm_reg_kernel.h, gemm_glds_kernel.h, conv_rowhalo.hip, splitk_reduce.hip,
+// conv_pp.hip, gemm_ring.hip) and of their launcher (gemm_conv.hip): problem descriptor, block -> tile mapping, LDS swizzle, epilogues,
+// and what each kernel file exports to the launcher.
 #pragma once
-#include "crg_common.h"
+#include "buf_access.h"
 #include "gemm_plan.h"
 #include <type_traits>
 
 namespace crg_mm {
+using namespace crg_buf;  // address-space pointers, buffer-descriptor access, wait_vmcnt<N>
 
 struct GemmP {
   const void* a; const void* a_lo; long lda, a_bs;
@@ -65,7 +67,6 @@ struct GemmP {
 constexpr int BM = 128;
 constexpr int BK = 64;
 static_assert(BM == 128 && BK == crg_plan::BK, "the planner (gemm_plan.h) counts 128-row tiles and k-tiles of crg_plan::BK");
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Block -> (m-tile, n-tile, k-slice).  The dispatcher deals workgroups round-robin to the 8 XCDs (block L runs on XCD
 // L % 8) and every XCD has its own 4 MB L2, so whatever two XCDs both touch is fetched twice over the fabric.  The host
@@ -564,12 +565,19 @@ __device__ __forceinline__ f32x2 ln_row_coeffs(const float* stat, long m, int pa
 #endif
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {  // s_waitcnt vmcnt(N) only (expcnt / lgkmcnt fields left at "no wait")
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
+// ---- what the kernel files export to the launcher (gemm_conv.hip) ----------------------------------------------------------------
+// One picker per kernel family: the kernel the planned launch names (the plan's selectors, gemm_plan.h), or null where the family has
+// none for them.  A kernel exists because its family's picker names it.
+typedef void (*KernFn)(GemmP);
+// conv_rowhalo.hip (gemm_reg_kernel.h): gemm_kernel (register-staged: fp32 A, or split-bf16 on two k-groups)
+KernFn pick_reg(const crg_plan::Launch& L, bool conv);
+// gemm_glds_gemm.hip / gemm_glds_conv.hip: gemm_glds_kernel<.., CONV = false / true> (gemm_glds_kernel.h)
+KernFn pick_glds_gemm(const crg_plan::Launch& L);
+KernFn pick_glds_conv(const crg_plan::Launch& L);
+// conv_rowhalo.hip: conv3_rowhalo_kernel (convs on 128- / 160-wide tiles only)
+KernFn pick_rowhalo(const crg_plan::Launch& L);
+// splitk_reduce.hip: the reduce launch behind a split-K launch (whole problem, or - tail split - the rows >= slab_row0)
+int launch_reduce(crg_ctx* ctx, hipStream_t st, const GemmP& p, const crg_plan::Plan& pl, int batch, bool y_f32);
 // conv_pp.hip: 3x3 / stride 1 conv on 256-pixel tiles, 4-slot weight ring + halo'd row buffers, the two waves of a SIMD half a k-tile
 // apart (bf16), launched in place of conv3_rowhalo_kernel<.., MT = 2>
 int launch_conv_pp(crg_ctx* ctx, hipStream_t st, const GemmP& p, int wnt);

@@ -32,68 +32,11 @@ struct LnGemmP {
   bf16* vt; int vt_n0, vt_T; long vt_ld; unsigned vt_bytes;
 };
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-static __device__ __forceinline__ void ln_dma16(const void* base, unsigned bytes, char* lds, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lptr_t)lds, 16, voff, soff, 0, 0);
+#ifdef CRG_LN_ABL_NOSTORE  // timing ablation only: every 8-byte epilogue store goes out of range (buf_store8<true>)
+constexpr bool LN_DROP8 = true;
+#else
+constexpr bool LN_DROP8 = false;
 #endif
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-// Epilogue stores through a buffer descriptor: an out-of-range lane (row >= M, column group >= N: offset forced past the end) is
-// DROPPED by the range check, so the store INSTRUCTION COUNT per wave is a compile-time constant whatever the tails are -
-// which is what lets the counted vmcnt waits below leave exactly these stores in flight (vmcnt counts stores on gfx950).
-static __device__ __forceinline__ void ln_store16(void* base, unsigned bytes, int voff, const bf16x8& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
-  u32x4 r;
-  __builtin_memcpy(&r, &v, 16);
-  __builtin_amdgcn_raw_buffer_store_b128(r, rs, voff, 0, 0);
-#endif
-}
-static __device__ __forceinline__ void ln_store8(void* base, unsigned bytes, int voff, const bf16x4& v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
-  u32x2 r;
-  __builtin_memcpy(&r, &v, 8);
-#ifdef CRG_LN_ABL_NOSTORE  // timing ablation only: every 8-byte store goes out of range (dropped by the range check, still counted in vmcnt)
-  voff = (int)0x80000000;
-#endif
-  __builtin_amdgcn_raw_buffer_store_b64(r, rs, voff, 0, 0);
-#endif
-}
-
-static __device__ __forceinline__ bf16x8 ln_load16(const void* base, unsigned bytes, int voff) {
-  bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-  __builtin_memcpy(&v, &r, 16);
-#endif
-  return v;
-}
-static __device__ __forceinline__ bf16x4 ln_load8(const void* base, unsigned bytes, int voff) {
-  bf16x4 v = {0, 0, 0, 0};
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-  const u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0);
-  __builtin_memcpy(&v, &r, 8);
-#endif
-  return v;
-}
-
-static __device__ __forceinline__ void ln_store2(void* base, unsigned bytes, int voff, bf16 v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const auto rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
-  short r;
-  __builtin_memcpy(&r, &v, 2);
-  __builtin_amdgcn_raw_buffer_store_b16(r, rs, voff, 0, 0);
-#endif
-}
-
 static __device__ __forceinline__ void ln_wait(int n) {  // wave-uniform s_waitcnt vmcnt(n); n outside the table waits for everything
   switch (n) {
     case 0: wait_vmcnt<0>(); break;
@@ -198,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
     const int kt = pa >> 4, rg = pa & 15;
     const int row = m0 + rg * 8 + rsub;
     const int vo = row < p.M ? (int)((long)row * p.ldx * 2) + clog * 16 : OOB;
-    ln_dma16(p.x, p.x_bytes, Ares + kt * A_KT + rg * 1024, vo, kt * 128);
+    buf_dma16(p.x, p.x_bytes, Ares + kt * A_KT + rg * 1024, vo, kt * 128);
   }
   int wvo[WL];
 #pragma unroll
@@ -213,7 +156,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
     const int soff = (int)((long)nt * BN * p.ldw * 2) + kt * 128;  // rows past N fall beyond w_bytes: zero-filled
 #pragma unroll
     for (int q = 0; q < WL; ++q)
-      if ((wave + NW * q) < WRG) ln_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, wvo[q], soff);
+      if ((wave + NW * q) < WRG) buf_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, wvo[q], soff);
   };
   // (weight k-tiles past the last one: their rows lie beyond w_bytes, the DMA writes zeros into slots nobody reads - issuing them
   // anyway keeps every wait of the loop at its steady-state count and every fragment read unconditional)
@@ -392,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
             bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (bf16)(v[e] * crg_gelu_erf_f(g[e]));
-            ln_store8(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + jn) * 2) : OOBS, o);
+            buf_store8<LN_DROP8>(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + jn) * 2) : OOBS, o);
           }
         }
       } else if (p.vt && n0 >= p.vt_n0) {
@@ -411,7 +354,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
             for (int e = 0; e < 8; ++e) {
               const float v = e < 4 ? acc[2 * u2][j][e] : acc[2 * u2 + 1][j][e - 4];
               const float bsv = p.bias ? p.bias[n + e < p.N ? n + e : 0] : 0.f;
-              ln_store2(p.vt, p.vt_bytes, (n + e < p.N && m < p.M) ? (int)(((row0 + n + e) * p.vt_ld + tk) * 2) : OOBS, (bf16)(v + bsv));
+              buf_store2(p.vt, p.vt_bytes, (n + e < p.N && m < p.M) ? (int)(((row0 + n + e) * p.vt_ld + tk) * 2) : OOBS, (bf16)(v + bsv));
             }
           }
           if constexpr (WNT & 1) {
@@ -419,7 +362,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               const float bsv = p.bias ? p.bias[n + e < p.N ? n + e : 0] : 0.f;
-              ln_store2(p.vt, p.vt_bytes, (n + e < p.N && m < p.M) ? (int)(((row0 + n + e) * p.vt_ld + tk) * 2) : OOBS,
+              buf_store2(p.vt, p.vt_bytes, (n + e < p.N && m < p.M) ? (int)(((row0 + n + e) * p.vt_ld + tk) * 2) : OOBS,
                         (bf16)(acc[WNT - 1][j][e] + bsv));
             }
           }
@@ -440,7 +383,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
             const int m = m0 + wm * 32 + j * 16 + frow;
             f32x4 a4 = acc[2 * u2][j] + ba, b4 = acc[2 * u2 + 1][j] + bb;
             if (p.res) {  // out-of-range lanes read zeros (range check) and are dropped by the store below
-              const bf16x8 r8 = ln_load16(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOBS);
+              const bf16x8 r8 = buf_load16(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOBS);
 #pragma unroll
               for (int e = 0; e < 4; ++e) {
                 a4[e] += (float)r8[e];
@@ -453,7 +396,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
               o[e] = (bf16)a4[e];
               o[4 + e] = (bf16)b4[e];
             }
-            ln_store16(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOBS, o);
+            buf_store16(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOBS, o);
           }
         }
         if constexpr (WNT & 1) {
@@ -466,14 +409,14 @@ __global__ __launch_bounds__(512, 2) void lngemm_kernel(LnGemmP p) {
             const int m = m0 + wm * 32 + j * 16 + frow;
             f32x4 a4 = acc[WNT - 1][j] + ba;
             if (p.res) {
-              const bf16x4 r4 = ln_load8(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOBS);
+              const bf16x4 r4 = buf_load8(p.res, p.res_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldr + n) * 2) : OOBS);
 #pragma unroll
               for (int e = 0; e < 4; ++e) a4[e] += (float)r4[e];
             }
             bf16x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (bf16)a4[e];
-            ln_store8(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOBS, o);
+            buf_store8<LN_DROP8>(p.y, p.y_bytes, (nok && m < p.M) ? (int)(((long)m * p.ldy + n) * 2) : OOBS, o);
           }
         }
       }
@@ -532,7 +475,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_geglu_pp_kernel(LnGemmP p) {
     const int kt = pa >> 4, rg = pa & 15;
     const int row = m0 + rg * 8 + rsub;
     const int vo = row < p.M ? (int)((long)row * p.ldx * 2) + clog * 16 : OOB;
-    ln_dma16(p.x, p.x_bytes, Ares + kt * A_KT + rg * 1024, vo, kt * 128);
+    buf_dma16(p.x, p.x_bytes, Ares + kt * A_KT + rg * 1024, vo, kt * 128);
   }
   int wvo[2];
 #pragma unroll
@@ -542,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_geglu_pp_kernel(LnGemmP p) {
     char* ws = smem + ((u + 5) & (NSLOT - 1)) * WS_BYTES;
     const int soff = (int)((long)is_nt * BN * p.ldw * 2) + is_kt * 128;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) ln_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, wvo[q], soff);
+    for (int q = 0; q < 2; ++q) buf_dma16(p.w, p.w_bytes, ws + (wave + NW * q) * 1024, wvo[q], soff);
     if (++is_kt == KT) {
       is_kt = 0;
       ++is_nt;
@@ -636,7 +579,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_geglu_pp_kernel(LnGemmP p) {
 #pragma unroll
       for (int j = 0; j < WMT; ++j)
         xa[kt][ks][j] = *reinterpret_cast<const bf16x8*>(Ares + kt * A_KT + (lds_off(wm * 32 + j * 16 + frow, fq) ^ (ks << 6)));
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+  wait_lgkmcnt0();
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();        // every wave holds its fragments: the rows' LDS becomes ring slots 0 .. 4
   asm volatile("" ::: "memory");
@@ -686,7 +629,7 @@ __global__ __launch_bounds__(512, 2) void lngemm_geglu_pp_kernel(LnGemmP p) {
     bf16x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (bf16)(v[e] * crg_gelu_erf_f(g[e]));
-    ln_store8(p.y, p.y_bytes, m < p.M ? (int)(((long)m * p.ldy + jn) * 2) : OOB, o);
+    buf_store8<LN_DROP8>(p.y, p.y_bytes, m < p.M ? (int)(((long)m * p.ldy + jn) * 2) : OOB, o);
     acc[2 * u2][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     acc[2 * u2 + 1][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   };

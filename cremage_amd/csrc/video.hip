@@ -26,6 +26,8 @@ namespace {
 using crg_mm::BK;
 using crg_mm::lds_off;
 using crg_mm::wait_vmcnt;
+using crg_mm::gptr_t;
+using crg_mm::lptr_t;
 
 struct CfP {
   const bf16* x; const bf16* w; const float* bias; const float* cvec; long cvec_ld;
@@ -43,8 +45,6 @@ __global__ __launch_bounds__(256, 2) void conv_frames_kernel(const CfP p) {
   constexpr int XS_BYTES = CF_BM * 128, STAGE_BYTES = XS_BYTES + BN * 128;
   constexpr int XL = CF_BM / 32, WL = BN / 32;  // 8-row groups (one 1 KiB wave-instruction each) per wave and k-tile
   extern __shared__ __attribute__((aligned(16))) char cf_smem[];
-  typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);

@@ -318,7 +318,7 @@ def packed_weight(w: torch.Tensor, kind: int, split: bool) -> Tuple[torch.Tensor
 # The fp32-class 3x3 conv in two matrix passes' worth of cycles instead of three: operands as a fp16 plane plus a plane of e4m3 pairs
 # (include/crg_hip.h, crg_split_mx).  Activations behind GroupNorm + SiLU are O(1): fixed power-of-two scales (hi8: x * 2^4, saturating at
 # |x| = 28 - the cross terms lose precision there, nothing else; lo8: (x - half(x)) * 2^15).  Weights: scales from the tensor's maximum at
-# pack time.  Correct and validated (tests/test_hip_ops.py::test_conv_mx) but measured 7-18 % slower than bf16 x 3 in round 4 (gemm_conv.hip,
+# pack time.  Correct and validated (tests/test_hip_ops.py::test_conv_mx) but measured 7-18 % slower than bf16 x 3 in round 4 (conv_rowhalo.hip,
 # conv3_rowhalo_kernel<.., MX>: status note), so the VAE uses it only under CRG_VAE_MX=1.
 VAE_MX = __import__("os").environ.get("CRG_VAE_MX", "0") != "0"
 MX_X_LOG2 = (4, 15)

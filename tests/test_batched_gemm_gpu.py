@@ -1,7 +1,7 @@
 """Kernel-level parity of the batched, strided crg_gemm (batch > 1, a_bstride / w_bstride / y_bstride / r_bstride, ldy != N) and of the row
 softmax between its two uses: the path of `ops.attention`'s unfused branch (every fp32 attention, the VAE AttnBlock) and of
 `ops.linear_transposed`.  The whole-network goldens reach these shapes with a whole network's tolerance; here every branch of
-gemm_conv.hip's `choose_splits` / `launch` / `launch_kernel` / `splitk_reduce_kernel` that a batch can reach is compared on its own:
+the GEMM planner's split-K choice (gemm_plan.h), gemm_conv.hip's launcher and splitk_reduce.hip's `splitk_reduce_kernel` that a batch can reach is compared on its own:
 
   A  raw crg_gemm through `ops._gemm` (the ctypes struct the wrappers fill) with explicit strides, on buffers LARGER than the operands:
      what belongs to no operand holds NaN on the input side and a sentinel on the output side, which must survive bitwise

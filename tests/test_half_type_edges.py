@@ -50,7 +50,7 @@ def _planes(t, flush):
 
 
 def _three_pass(op, x, w, flush=False):
-    """CPU emulation of the fp32-class product as gemm_conv.hip states it: three matrix passes hi*hi + hi*lo + lo*hi on half-type
+    """CPU emulation of the fp32-class product as gemm_reg_kernel.h states it: three matrix passes hi*hi + hi*lo + lo*hi on half-type
     planes (lo*lo dropped), fp32 accumulate, fp32 result.  `op(x, w)` is the bias-free linear map in the dtype of its arguments."""
     xh, xl = _planes(x, flush)
     wh, wl = _planes(w, flush)

@@ -83,7 +83,7 @@ def assert_route(what, **want):
 # ------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(128, 160, 64), (300, 320, 328), (77, 128, 768), (8, 1280, 320), (1000, 200, 72), (130, 36, 40),
-                                   # one shape per tile configuration of the LDS-DMA kernel (gemm_conv.hip `launch`):
+                                   # one shape per tile configuration of the LDS-DMA kernel (gemm_glds_kernel.h; chosen by gemm_plan.h):
                                    (3000, 1280, 320),   # 192 tiles, short K          -> D (64-row tiles, 4 waves)
                                    (8200, 1280, 136),   # 520 tiles                   -> A (4 waves, 2 blocks per CU)
                                    (2048, 640, 1280),   # 64 tiles, short K           -> C (64-row tiles, 8 waves)

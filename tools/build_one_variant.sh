@@ -1,6 +1,7 @@
 #!/bin/bash
 # Dev helper: rebuild ONE source of the working tree with extra compiler flags and link it against the other (default-build) objects
 # into tools/ab/libcrg_<tag>.so.  Usage: tools/build_one_variant.sh <tag> <source stem, e.g. conv_pp> [-DNAME=VALUE ...]
+# (a knob of a header that several units include - CRG_LB_A, CRG_GEMM_NOPF: gemm_glds_kernel.h - needs tools/build_variant.sh, which rebuilds them all)
 set -eo pipefail
 TAG=$1; SRC=$2; shift; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
