@@ -198,6 +198,18 @@ class ConvFramesArgs(C.Structure):
     ]
 
 
+class ConvFramesX3Args(C.Structure):
+    _fields_ = [
+        ("x_hi", c_void_p), ("x_lo", c_void_p),
+        ("w_hi", c_void_p), ("w_lo", c_void_p),
+        ("bias", c_void_p),
+        ("cvec", c_void_p), ("cvec_ld", c_int64),
+        ("residual", c_void_p), ("rscale", c_void_p),
+        ("y", c_void_p),
+        ("b", c_int), ("T", c_int), ("S", c_int), ("Cin", c_int), ("Cout", c_int),
+    ]
+
+
 class AttnFramesArgs(C.Structure):
     _fields_ = [
         ("q", c_void_p), ("ldq", c_int64),
@@ -293,6 +305,8 @@ SIGNATURES = {
     "crg_attention_frames": (c_int, [c_void_p, c_void_p, C.POINTER(AttnFramesArgs)]),
     "crg_add_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int]),
     "crg_lincomb_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int]),
+    "crg_conv_frames_x3": (c_int, [c_void_p, c_void_p, C.POINTER(ConvFramesX3Args)]),
+    "crg_conv_frames_thin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
 }
 
 

@@ -1877,7 +1877,8 @@ def conv_frames(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
     y[v, t] = sum_d W_d x[v, t + d] + bias + cvec[v * frames + t], then y = residual + rscale[v * frames + t] * y when a residual is given
     (rscale None = 1).  cvec: [b * frames, Cout], rscale: b * frames values, residual: like y.  A frame outside its video contributes zero
     by selection - its memory is never read.  Half type: one launch of crg_conv_frames.  fp32: composed from the fp32-class ops, per
-    video three row-shifted `linear` calls summed in fp32 (not the hot path: the video nets run in the half type)."""
+    video three row-shifted `linear` calls summed in fp32 (the video UNet runs in the half type; the fp32-class video VAE holds
+    pre-split planes and calls `conv_frames_x3`, one launch)."""
     _need_cuda(x, weight, bias, cvec, residual, rscale)
     b, F, S, Cin = _frame_tokens(x, frames, "conv_frames")
     Cout = weight.shape[0]
@@ -1918,6 +1919,62 @@ def conv_frames(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tens
                          residual=residual.data_ptr() if residual is not None else None, rscale=rs.data_ptr() if rs is not None else None,
                          y=y.data_ptr(), b=b, T=frames, S=S, Cin=Cin, Cout=Cout)
     L.check(L.load().crg_conv_frames(h, _st(), C.byref(a)), h, "crg_conv_frames")
+    return y
+
+
+def conv_frames_x3(x_hi: torch.Tensor, x_lo: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, frames: int,
+                   cvec: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, rscale: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`conv_frames` in the fp32 class, one launch of crg_conv_frames_x3: x_hi, x_lo are the two half-type planes [b * frames, S, Cin] of an
+    fp32 activation (group_norm(split=True) / split_bf16, as tokens), the weight's planes come from the pack cache, residual and result
+    are fp32 [b * frames, S, Cout].  `out`: write there instead of a new tensor (it may be the residual itself)."""
+    _need_cuda(x_hi, x_lo, weight, bias, cvec, residual, rscale, out)
+    if x_hi.dtype != HALF or x_lo.dtype != HALF or x_hi.shape != x_lo.shape or not x_lo.is_contiguous():
+        raise L.CrgError(f"conv_frames_x3: x_hi / x_lo must be two contiguous half-type planes of one shape, got {tuple(x_hi.shape)} {x_hi.dtype} "
+                         f"and {tuple(x_lo.shape)} {x_lo.dtype}")
+    b, F, S, Cin = _frame_tokens(x_hi, frames, "conv_frames_x3")
+    Cout = weight.shape[0]
+    if weight.shape[1] != Cin:
+        raise L.CrgError(f"conv_frames_x3: weight {tuple(weight.shape)} does not match {Cin} input channels")
+    if Cin % 32 or Cout % 32:
+        raise L.CrgError(f"conv_frames_x3: Cin={Cin} / Cout={Cout} must be multiples of 32")
+    if rscale is not None and residual is None:
+        raise L.CrgError("conv_frames_x3: rscale needs a residual")
+    for t, what in ((residual, "residual"), (out, "out")):
+        if t is not None and (t.shape != (F, S, Cout) or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise L.CrgError(f"conv_frames_x3: {what} must be contiguous fp32 [{F}, {S}, {Cout}]")
+    if cvec is not None:
+        if cvec.numel() != F * Cout:
+            raise L.CrgError(f"conv_frames_x3: cvec must hold [{F}, {Cout}] values, got {tuple(cvec.shape)}")
+        cvec = cvec.detach().reshape(F, Cout).float().contiguous()
+    rs = _frame_vec(rscale, F, "conv_frames_x3: rscale")
+    hi, lo = packed_weight(frames_weight(weight), L.PACK_LINEAR, True)
+    bb = f32_vec(bias)
+    y = out if out is not None else torch.empty((F, S, Cout), dtype=torch.float32, device=x_hi.device)
+    h = _h(x_hi)
+    a = L.ConvFramesX3Args(x_hi=x_hi.data_ptr(), x_lo=x_lo.data_ptr(), w_hi=hi.data_ptr(), w_lo=lo.data_ptr(),
+                           bias=bb.data_ptr() if bb is not None else None, cvec=cvec.data_ptr() if cvec is not None else None, cvec_ld=Cout,
+                           residual=residual.data_ptr() if residual is not None else None, rscale=rs.data_ptr() if rs is not None else None,
+                           y=y.data_ptr(), b=b, T=frames, S=S, Cin=Cin, Cout=Cout)
+    L.check(L.load().crg_conv_frames_x3(h, _st(), C.byref(a)), h, "crg_conv_frames_x3")
+    return _written(y) if out is not None else y
+
+
+def conv_frames_thin(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, frames: int) -> torch.Tensor:
+    """The (3, 1, 1) frame conv on C <= 8 channels (AE3DConv.time_mix_conv): x [b * frames, S, C] tokens, half type or fp32; weight
+    [C, C, 3, 1, 1] and bias are taken in fp32.  fp32 FMAs in a fixed order, one rounding to x.dtype; frames outside a video are not read."""
+    _need_cuda(x, weight, bias)
+    b, F, S, Cc = _frame_tokens(x, frames, "conv_frames_thin")
+    if not 1 <= Cc <= 8:
+        raise L.CrgError(f"conv_frames_thin: {Cc} channels (1 .. 8; wider convs are conv_frames)")
+    if weight.dim() not in (3, 5) or weight.shape[0] != Cc or weight.shape[1] != Cc or weight[0, 0].numel() != 3:
+        raise L.CrgError(f"conv_frames_thin: a [{Cc}, {Cc}, 3, 1, 1] weight expected, got {tuple(weight.shape)}")
+    if bias is not None and bias.numel() != Cc:
+        raise L.CrgError(f"conv_frames_thin: {bias.numel()} bias values for {Cc} channels")
+    w = f32_vec(weight)
+    y = torch.empty_like(x)
+    h = _h(x)
+    L.check(L.load().crg_conv_frames_thin(h, _st(), _p(x), _p(w), _p(f32_vec(bias)), _p(y), b, frames, S, Cc, _act_dt(x)), h, "crg_conv_frames_thin")
     return y
 
 

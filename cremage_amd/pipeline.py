@@ -387,12 +387,55 @@ SVD_XT_UNET = dict(adm_in_channels=768, num_classes="sequential", use_checkpoint
 def build_synthetic_svd(unet_cfg=None, device="cuda", unet_dtype=torch.bfloat16, seed: int = 1234, fill: bool = True):
     """The SVD-XT video UNet (cremage_amd.sgm_hip.video.VideoUNet, 1.52 B parameters at the default configuration) with name-keyed
     synthetic weights.  The network alone: its inputs - CLIP image embedding, VAE-encoded conditioning frames, the fps / motion /
-    augmentation vector - are the caller's tensors, and the latent frames it denoises go to the reference's VideoDecoder."""
+    augmentation vector - are the caller's tensors; the latent frames it denoises go to a VideoDecoder (`build_synthetic_svd_vae` /
+    `decode_video` below, or the reference's)."""
     from .sgm_hip.video import VideoUNet
     unet = VideoUNet(**(unet_cfg or SVD_XT_UNET))
     if fill:
         synth_fill_(unet, seed, prefix="svd_unet.")
     return unet.to(unet_dtype).to(device).eval()
+
+
+# svd_xt_1_1.yaml first_stage_config: the SD VAE encoder and the VideoDecoder on the same ddconfig
+SVD_VAE_DD = dict(attn_type="vanilla", double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128, ch_mult=[1, 2, 4, 4],
+                  num_res_blocks=2, attn_resolutions=[], dropout=0.0)
+
+
+def svd_first_stage_config(dd=None, video_kernel_size=(3, 1, 1), **decoder_kw) -> dict:
+    """first_stage_config of configs/svd_xt_vae-hip.yaml as a dict (`dd`: another ddconfig, e.g. a narrower one)"""
+    dd = dict(dd or SVD_VAE_DD)
+    return {"target": "cremage_amd.sgm_hip.video_vae.AutoencodingEngine",
+            "params": {"loss_config": {"target": "torch.nn.Identity"},
+                       "regularizer_config": {"target": "cremage_amd.sgm_hip.video_vae.DiagonalGaussianRegularizer"},
+                       "encoder_config": {"target": "cremage_amd.ldm_hip.vae.Encoder", "params": dd},
+                       "decoder_config": {"target": "cremage_amd.sgm_hip.video_vae.VideoDecoder",
+                                          "params": dict(dd, video_kernel_size=list(video_kernel_size), **decoder_kw)}}}
+
+
+def build_synthetic_svd_vae(dd=None, device="cuda", vae_dtype=torch.float32, seed: int = 1234, fill: bool = True, **decoder_kw):
+    """The SVD first stage (cremage_amd.sgm_hip.video_vae.AutoencodingEngine: SD VAE encoder + VideoDecoder) with name-keyed synthetic
+    weights - the fill re-randomises the zero-initialised second conv of every time_stack and draws `mix_factor` like any parameter, so
+    the temporal branch takes part.  fp32 parameters select the fp32-class kernels, as for the image VAE."""
+    from .ldm_hip.latent_diffusion import instantiate_from_config
+    fs = instantiate_from_config(svd_first_stage_config(dd, **decoder_kw))
+    if fill:
+        synth_fill_(fs, seed, prefix="svd_vae.")
+    return fs.to(vae_dtype).to(device).eval()
+
+
+@torch.no_grad()
+def decode_video(first_stage, z: torch.Tensor, scale_factor: float = 0.18215, decoding_t: Optional[int] = None) -> torch.Tensor:
+    """`DiffusionEngine.decode_first_stage` (sgm/models/diffusion.py:118-136) for a VideoDecoder first stage: latent frames [F, 4, h, w]
+    -> frames [F, 3, 8 h, 8 w] fp32, `decoding_t` (en_and_decode_n_samples_a_time) frames per decoder call, all of them when None.
+    Each chunk is decoded as ONE video of len(chunk) frames: its frame convs zero-pad at the chunk's ends, exactly as the reference's
+    do - chunked and unchunked decodes differ there by construction."""
+    z = 1.0 / scale_factor * z
+    n = z.shape[0] if not decoding_t else int(decoding_t)
+    out = []
+    for i in range(0, z.shape[0], n):
+        chunk = z[i:i + n]
+        out.append(first_stage.decode(chunk, timesteps=len(chunk)))
+    return torch.cat(out, dim=0)
 
 
 @torch.no_grad()

@@ -754,6 +754,35 @@ int crg_add_frames(crg_ctx* ctx, void* stream, const void* x, const void* e, voi
 int crg_lincomb_frames(crg_ctx* ctx, void* stream, const float* a, const void* x, const float* c, const void* z, void* y, int64_t frames,
                        int64_t per_frame, int dtype);
 
+/* ---- temporal layers of the video VAE decoder (video_x3.hip) ---------------------------------------------------------------------------
+ * Rows as above: video v, frame t, pixel s at row (v*T + t)*S + s.
+ *
+ * crg_conv_frames_x3: crg_conv_frames in the fp32 class - same formula, same zero padding BY SELECTION (a frame outside its video is never
+ *   addressed).  x arrives as the two half-type planes x_hi, x_lo [b*T*S][Cin] that crg_groupnorm_split / crg_split_bf16 write; w as the
+ *   planes w_hi, w_lo [Cout][3*Cin] of crg_pack_weight(CRG_PACK_LINEAR, split) applied to the tap-major matrix of crg_conv_frames; bias,
+ *   cvec, rscale fp32 as there; residual fp32 [b*T*S][Cout] or NULL; y fp32 [b*T*S][Cout], may alias residual.  Three matrix passes
+ *   lo*hi + hi*lo + hi*hi per k-step into one fp32 accumulator over the whole K = 3*Cin in one block, fixed order, no split-K; the tile
+ *   shape depends on Cout alone (batch-invariant with the mode on or off).
+ *   Domain: that of crg_conv_frames; y must not overlap x_hi / x_lo, nor the residual at an offset (-22).  Profile slot: CRG_K_GEMM_X3.
+ *
+ * crg_conv_frames_thin: the same conv on C <= 8 channels (AE3DConv.time_mix_conv, the decoder's 3 pixel channels).  x, y `dtype`
+ *   (CRG_BF16 = the half type, or CRG_F32) [b*T*S][C], y must not overlap x anywhere (-22); w fp32 [C][C][3] (the Conv3d weight [C][C][3][1][1]); bias fp32
+ *   [C] or NULL.  One thread per pixel: y = bias, then for tap d = -1, 0, 1 (skipped when frame t + d is outside the video: never read)
+ *   and input channel ci in ascending order  y[co] = fma(w[co][ci][d], x[v,t+d,s,ci], y[co])  in fp32, rounded once to `dtype`.
+ *   Profile slot: CRG_K_ELEMENTWISE. */
+typedef struct {
+  const void* x_hi; const void* x_lo;
+  const void* w_hi; const void* w_lo;
+  const float* bias;
+  const float* cvec; int64_t cvec_ld;
+  const void* residual; const float* rscale;
+  void* y;
+  int b, T, S, Cin, Cout;
+} crg_conv_frames_x3_args;
+int crg_conv_frames_x3(crg_ctx* ctx, void* stream, const crg_conv_frames_x3_args* args);
+int crg_conv_frames_thin(crg_ctx* ctx, void* stream, const void* x, const float* w, const float* bias, void* y, int b, int T, int S, int C,
+                         int dtype);
+
 #ifdef __cplusplus
 }
 #endif
