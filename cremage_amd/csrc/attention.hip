@@ -20,6 +20,7 @@
 //
 // LDS: K tile [64][KS*16] with rows padded to 16*(2KS+1) bytes, V^T tile [NV*32][64] with rows padded
 // to 136 bytes: both fragment read patterns are bank-conflict free (guide §2 bank rules).
+#include "attention_plan.h"
 #include "buf_access.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -918,8 +919,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_dma_kernel(AttnP p, unsigne
 }
 
 template <int KC, int NV, int OCC, int SUB, int NW>
-int launch_attn_dma(crg_ctx* ctx, hipStream_t st, const AttnP& p) {
-  dim3 grid((p.Nq + 32 * NW - 1) / (32 * NW), p.B * p.H);
+int launch_attn_dma(crg_ctx* ctx, hipStream_t st, const AttnP& p, const crg_attn_plan::Plan& pl) {
+  dim3 grid(pl.grid_x, pl.grid_y);
   const unsigned k_bytes = (unsigned)((((long)p.Nk - 1) * p.ldk + p.Dh) * 2);
   const unsigned v_bytes = (unsigned)((((long)p.Dh - 1) * p.ldvt + (p.Nk + 7) / 8 * 8) * 2);  // whole 16-byte chunks (ldvt >= roundup(Nk, 8))
   hipLaunchKernelGGL((attn_dma_kernel<KC, NV, (KC * 8 < NV * 32), OCC, SUB, NW>), grid, dim3(64 * NW), 0, st, p, k_bytes, v_bytes);
@@ -1254,8 +1255,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_sp_kernel(AttnP p, unsigned
 }
 
 template <int KC, int NV, int NW, int OCC>
-int launch_attn_sp(crg_ctx* ctx, hipStream_t st, const AttnP& p) {
-  dim3 grid((p.Nq + 32 * NW - 1) / (32 * NW), p.B * p.H);
+int launch_attn_sp(crg_ctx* ctx, hipStream_t st, const AttnP& p, const crg_attn_plan::Plan& pl) {
+  dim3 grid(pl.grid_x, pl.grid_y);
   const unsigned k_bytes = (unsigned)((((long)p.Nk - 1) * p.ldk + p.Dh) * 2);
   const unsigned v_bytes = (unsigned)((((long)p.Dh - 1) * p.ldvt + (p.Nk + 7) / 8 * 8) * 2);  // whole 16-byte chunks (ldvt >= roundup(Nk, 8))
   hipLaunchKernelGGL((attn_sp_kernel<KC, NV, (KC * 8 < NV * 32), NW, OCC>), grid, dim3(64 * NW), 0, st, p, k_bytes, v_bytes);
@@ -1264,19 +1265,14 @@ int launch_attn_sp(crg_ctx* ctx, hipStream_t st, const AttnP& p) {
 }
 
 template <int KS, int NV>
-int launch_attn_ctx(crg_ctx* ctx, hipStream_t st, const AttnP& p, bool vrm) {
-  // blocks per (batch, head): the largest divisor of the 128-query group count that keeps the grid within four blocks per CU,
-  // so that every block walks the same number of groups behind ONE staging of the key tiles
-  const int nqg = (p.Nq + 127) / 128, bh = p.B * p.H;
-  int gx = 1;
-  for (int d = 1; d <= nqg; ++d)
-    if (nqg % d == 0 && (long)d * bh <= 1024) gx = d;
-  dim3 grid(gx, bh);
-  if (vrm) {
-    if (p.Dh < NV * 32) hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, true, true>), grid, dim3(256), 0, st, p);
+int launch_attn_ctx(crg_ctx* ctx, hipStream_t st, const AttnP& p, const crg_attn_plan::Plan& pl) {
+  dim3 grid(pl.grid_x, pl.grid_y);  // (grid_x: attention_plan.h, the divisor of the query-group count)
+  const crg_attn_plan::Variant& v = crg_attn_plan::VARIANTS[pl.variant];
+  if (v.vrm) {
+    if (v.ones) hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, true, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, false, true>), grid, dim3(256), 0, st, p);
   } else {
-    if (p.Dh < NV * 32) hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, true, false>), grid, dim3(256), 0, st, p);
+    if (v.ones) hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, true, false>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_ctx_kernel<KS, NV, false, false>), grid, dim3(256), 0, st, p);
   }
   CRG_CHECK_LAUNCH(ctx, "attention (few keys)");
@@ -1284,13 +1280,14 @@ int launch_attn_ctx(crg_ctx* ctx, hipStream_t st, const AttnP& p, bool vrm) {
 }
 
 template <int KS, int NV>
-int launch_attn(crg_ctx* ctx, hipStream_t st, const AttnP& p, bool vrm) {
-  dim3 grid((p.Nq + 127) / 128, p.B * p.H);
-  if (vrm) {
-    if (p.Dh < NV * 32) hipLaunchKernelGGL((attn_kernel<KS, NV, true, true>), grid, dim3(256), 0, st, p);
+int launch_attn(crg_ctx* ctx, hipStream_t st, const AttnP& p, const crg_attn_plan::Plan& pl) {
+  dim3 grid(pl.grid_x, pl.grid_y);
+  const crg_attn_plan::Variant& v = crg_attn_plan::VARIANTS[pl.variant];
+  if (v.vrm) {
+    if (v.ones) hipLaunchKernelGGL((attn_kernel<KS, NV, true, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_kernel<KS, NV, false, true>), grid, dim3(256), 0, st, p);
   } else {
-    if (p.Dh < NV * 32) hipLaunchKernelGGL((attn_kernel<KS, NV, true>), grid, dim3(256), 0, st, p);
+    if (v.ones) hipLaunchKernelGGL((attn_kernel<KS, NV, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((attn_kernel<KS, NV, false>), grid, dim3(256), 0, st, p);
   }
   CRG_CHECK_LAUNCH(ctx, "attention");
@@ -1315,64 +1312,28 @@ static int attention_entry(crg_ctx* ctx, void* stream, const void* q, int64_t ld
   const double flops = 4.0 * B * H * (double)Nq * Nk * Dh;
   const double bytes = 2.0 * B * H * Dh * (2.0 * Nq + 2.0 * Nk);
   crg_prof_scope ps(ctx, st, CRG_K_ATTN, flops, bytes);
-  const int ks = (Dh + 15) / 16;
-  // few keys (cross-attention against the prompt context, FaceID tokens, 8x8 self-attention): K / V staged once per block, no barrier
-  // in the loop.  CRG_ATTN_CTX (developer knob): 0 = the general kernels for these shapes too
-  static const int use_ctx = getenv("CRG_ATTN_CTX") ? atoi(getenv("CRG_ATTN_CTX")) : 1;
-  // ... used where a block then walks at least two query groups behind one staging of the keys (measured, kernel trace: 8 x 4096
-  // queries x 77 keys, d 40: 22.3 -> 19.6 us; with ONE group per block - 1024 queries, d 80 - the general kernel's interior-tile
-  // staging is the faster one, 12.6 vs 13.5 us).  These launches are bound by their 80-byte-per-head Q / O row slices (32 cache
-  // lines per wave-instruction), not by block count: see DESIGN 4.
-  const int nqg_ = (Nq + 127) / 128;
-  // (batch-invariant mode: the block count of tune_samples samples, crg_heur_samples - the two kernels sum the keys in different orders)
-  if (use_ctx && Nk <= 128 && (long)nqg_ * crg_heur_samples(ctx, B) * H >= 2048) {
-    switch (ks) {
-      case 1: return launch_attn_ctx<1, 1>(ctx, st, p, vrm);
-      case 2: return launch_attn_ctx<2, 1>(ctx, st, p, vrm);
-      case 3: return launch_attn_ctx<3, 2>(ctx, st, p, vrm);
-      case 4: return launch_attn_ctx<4, 2>(ctx, st, p, vrm);
-      case 5: return launch_attn_ctx<5, 3>(ctx, st, p, vrm);
-      case 6: return launch_attn_ctx<6, 3>(ctx, st, p, vrm);
-      case 7: return launch_attn_ctx<7, 4>(ctx, st, p, vrm);
-      case 8: return launch_attn_ctx<8, 4>(ctx, st, p, vrm);
-      case 9: return launch_attn_ctx<9, 5>(ctx, st, p, vrm);
-      case 10: return launch_attn_ctx<10, 5>(ctx, st, p, vrm);
-    }
-  }
-  // LDS-DMA forms: transposed V, whole 64-key tiles, extents addressable through a 32-bit buffer descriptor.
-  // CRG_ATTN_DMA (developer knob): 0 = register-staged kernel only, 1 (default) = software-pipelined where instantiated, else the
-  // plain LDS-DMA kernel, 8 / 4 = plain LDS-DMA kernel on 8 / 4 waves
-  static const int use_dma = getenv("CRG_ATTN_DMA") ? atoi(getenv("CRG_ATTN_DMA")) : 1;
-  static const int dma_tail = getenv("CRG_ATTN_TAIL") ? atoi(getenv("CRG_ATTN_TAIL")) : 1;  // key tails on the LDS-DMA kernel (0: register-staged)
-  if (use_dma && !vrm && (Nk % 64 == 0 || (dma_tail && Nk > 8)) && ((long)Nk * ldk * 2 < (1l << 31)) && ((long)Dh * ldv * 2 < (1l << 31))) {
-    const bool sp = use_dma == 1 && Nk % 128 == 0;
-    static const int use_occ4 = getenv("CRG_ATTN_OCC4") ? atoi(getenv("CRG_ATTN_OCC4")) : 1;
-    if (Dh == 40) {
-      if (sp) return use_occ4 ? launch_attn_sp<5, 2, 8, 4>(ctx, st, p) : launch_attn_sp<5, 2, 8, 2>(ctx, st, p);
-      // few key tiles (cross-attention: 77 keys): 128-query blocks, i.e. twice the blocks and four-wave barriers (19.2 vs 19.9 us)
-      return (use_dma == 4 || (use_dma == 1 && Nk <= 256)) ? launch_attn_dma<5, 2, 4, 1, 4>(ctx, st, p) : launch_attn_dma<5, 2, 4, 1, 8>(ctx, st, p);
-    }
-    if (Dh == 64) {  // measured (B4 N4096 h10: register-staged 256 us, pipelined 253, LDS-DMA on 8 waves 233, on 4 waves 226): plain form, 4 waves
-      if (use_dma == 5 && Nk % 128 == 0) return launch_attn_sp<8, 2, 8, 2>(ctx, st, p);
-      return use_dma == 8 ? launch_attn_dma<8, 2, 4, 1, 8>(ctx, st, p) : launch_attn_dma<8, 2, 4, 1, 4>(ctx, st, p);
-    }
-    if (Dh == 80) {
-      if (sp) return launch_attn_sp<10, 3, 8, 2>(ctx, st, p);
-      return use_dma == 4 ? launch_attn_dma<10, 3, 3, 1, 4>(ctx, st, p) : launch_attn_dma<10, 3, 2, 1, 8>(ctx, st, p);
-    }
-  }
-  switch (ks) {
-    case 1: return launch_attn<1, 1>(ctx, st, p, vrm);
-    case 2: return launch_attn<2, 1>(ctx, st, p, vrm);
-    case 3: return launch_attn<3, 2>(ctx, st, p, vrm);
-    case 4: return launch_attn<4, 2>(ctx, st, p, vrm);
-    case 5: return launch_attn<5, 3>(ctx, st, p, vrm);
-    case 6: return launch_attn<6, 3>(ctx, st, p, vrm);
-    case 7: return launch_attn<7, 4>(ctx, st, p, vrm);
-    case 8: return launch_attn<8, 4>(ctx, st, p, vrm);
-    case 9: return launch_attn<9, 5>(ctx, st, p, vrm);
-    case 10: return launch_attn<10, 5>(ctx, st, p, vrm);
-  }
+  // Developer knobs, read once per process; what they and the sizes decide is attention_plan.h's (plan_attention, with the measurements
+  // behind each rule).
+  static const crg_attn_plan::Knobs knobs = [] {
+    crg_attn_plan::Knobs kn;
+    if (getenv("CRG_ATTN_CTX")) kn.ctx = atoi(getenv("CRG_ATTN_CTX"));
+    if (getenv("CRG_ATTN_DMA")) kn.dma = atoi(getenv("CRG_ATTN_DMA"));
+    if (getenv("CRG_ATTN_TAIL")) kn.tail = atoi(getenv("CRG_ATTN_TAIL"));
+    if (getenv("CRG_ATTN_OCC4")) kn.occ4 = atoi(getenv("CRG_ATTN_OCC4"));
+    return kn;
+  }();
+  const crg_attn_plan::Plan pl = crg_attn_plan::plan_attention(B, H, Nq, Nk, Dh, (long)ldk, (long)ldv, vrm, crg_heur_samples(ctx, B), knobs);
+  if (pl.rc) return crg_fail(ctx, pl.rc, "%s", pl.msg);
+  // One case per row of the variant table.  The staged kernels' launchers hold the four ONES x VRM forms of their <KS, NV> and pick by the
+  // row's flags.
+#define CRG_ATTN_LAUNCH_CTX(KK, NV, ONES, VRM, NW, OCC, SUB) launch_attn_ctx<KK, NV>(ctx, st, p, pl)
+#define CRG_ATTN_LAUNCH_REG(KK, NV, ONES, VRM, NW, OCC, SUB) launch_attn<KK, NV>(ctx, st, p, pl)
+#define CRG_ATTN_LAUNCH_DMA(KK, NV, ONES, VRM, NW, OCC, SUB) launch_attn_dma<KK, NV, OCC, SUB, NW>(ctx, st, p, pl)
+#define CRG_ATTN_LAUNCH_SP(KK, NV, ONES, VRM, NW, OCC, SUB) launch_attn_sp<KK, NV, NW, OCC>(ctx, st, p, pl)
+#define CRG_ATTN_CASE(FAM, KK, NV, ONES, VRM, NW, OCC, SUB) \
+  case crg_attn_plan::V_##FAM##_##KK##_##NV##_##ONES##_##VRM##_##NW##_##OCC##_##SUB: return CRG_ATTN_LAUNCH_##FAM(KK, NV, ONES, VRM, NW, OCC, SUB);
+  switch (pl.variant) { CRG_ATTN_VARIANTS(CRG_ATTN_CASE) }
+#undef CRG_ATTN_CASE
   return crg_fail(ctx, -22, "attention: head dim %d unsupported", Dh);
 }
 

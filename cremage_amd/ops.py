@@ -1211,6 +1211,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
               flash: Optional[bool] = None) -> torch.Tensor:
     """softmax(Q K^T * scale) V with heads split along the channel dim.
     q: [B, Nq, C], k: [B, Nk, C], vt: [B, C, ld] (V transposed, ld = roundup(Nk, 8)) -> [B, Nq, C].
+    k may hold more than n_keys rows per batch: the first n_keys of every batch are the keys (with several batches that costs a copy).
     Pad columns n_keys..ld of vt: the flash branch (half type, d_head <= 160) masks keys >= n_keys and never reads them unmasked, so
     anything may sit there.  The unfused branch (fp32, or d_head > 160) does NOT mask: its PV GEMM runs over roundup(n_keys, 8)
     columns and multiplies the pads by the score buffer's pad columns, which are exact zeros - finite pads drop out bitwise,
@@ -1245,13 +1246,14 @@ def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int, n_
     ld = vt.shape[-1]
     h = _h(q)
     if flash:
-        # q / k may be column slices of one fused projection output: rows keep their parent stride
+        # q / k may be column slices of one fused projection output: rows keep their parent stride.  The kernels step from batch to batch
+        # by n_keys rows of k: a k buffer with more rows than n_keys is cut to them (and copied, unless there is one batch only)
         def rows(t):
-            if t.stride(2) != 1 or t.stride(0) != t.shape[1] * t.stride(1):
+            if t.stride(2) != 1 or (B > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
                 t = t.contiguous()
             return t, t.stride(1)
         q, ldq = rows(q)
-        k, ldk = rows(k)
+        k, ldk = rows(k[:, :n_keys])
         o = torch.empty((B, Nq, Cc), dtype=q.dtype, device=q.device)
         L.check(L.load().crg_attention(h, _st(), _p(q), ldq, _p(k), ldk, _p(vt), ld, _p(o), Cc, B, heads, Nq, n_keys, Dh, scale,
                                        L.BF16), h, "crg_attention")

@@ -2,12 +2,14 @@
 
 The library is chosen when cremage_amd is imported, so the fp16 run is ONE fresh child process: tests/test_hip_ops.py,
 tests/test_half_type_edges.py, tests/test_batched_gemm_gpu.py (all generic over the process's half type, fp16 bounds = bf16
-bounds / 8) and tests/test_exact_gpu.py (bitwise on exact operands: no bound to scale, the tie offset follows the type) plus the two fp32-class VAE goldens of tests/test_hip_models.py, whose three-pass convs then run on fp16 planes.  The child's first test establishes that it
+bounds / 8), tests/test_exact_gpu.py (bitwise on exact operands: no bound to scale, the tie offset follows the type) and
+tests/test_attention_exact_gpu.py (exact softmaxes: bitwise in either type; its five knob runs are grandchildren, one at a time) plus the two fp32-class VAE goldens of tests/test_hip_models.py, whose three-pass convs then run on fp16 planes.  The child's first test establishes that it
 really runs the fp16 library (test_half_type_edges.py::test_library_of_this_process_half_type).  test_linear_ring_gemm starts a
 grandchild that inherits CRG_HALF: at most three processes hold the GPU.
 
-Measured on MI355X: the child takes 36 s for its 505 cases, 1.2 s of them for the 45 of tests/test_batched_gemm_gpu.py and about 6 s
-for the 57 of tests/test_exact_gpu.py, most of that their fp64 CPU references (the whole `-m gpu` run: 174 s for 1246 cases; the
+Measured on MI355X: the child takes 40 s for its 777 cases, 1.2 s of them for the 45 of tests/test_batched_gemm_gpu.py, about 6 s
+for the 57 of tests/test_exact_gpu.py, most of that their fp64 CPU references, and 13 s for the 272 of
+tests/test_attention_exact_gpu.py when that file runs alone (the whole `-m gpu` run: 253 s for 1709 cases; the
 suite's limit is 900 s), so nothing is deselected; a
 parametrisation that had to be would be listed in DESELECT with its seconds, and the count below compares against the selection minus
 that list.
@@ -84,9 +86,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 SELECTION = ["tests/test_hip_ops.py", "tests/test_half_type_edges.py", "tests/test_batched_gemm_gpu.py", "tests/test_exact_gpu.py",
-             "tests/test_hip_models.py::test_vae_sd15_full_decode_pixels", "tests/test_hip_models.py::test_vae_sd15_full_encode"]
+             "tests/test_attention_exact_gpu.py", "tests/test_hip_models.py::test_vae_sd15_full_decode_pixels", "tests/test_hip_models.py::test_vae_sd15_full_encode"]
 DESELECT = []  # node ids (individual parametrisations only), each with its measured seconds
-CHILD_TIME_LIMIT = 80  # seconds: about twice the measured 37
+CHILD_TIME_LIMIT = 80  # seconds: about twice the measured 40
 
 
 def _pytest(extra, timeout):
@@ -103,7 +105,7 @@ def test_op_suite_against_the_fp16_library():
     m = re.search(r"^(\d+)(?:/\d+)? tests? collected", c.stdout, re.M)
     assert c.returncode == 0 and m, c.stdout[-3000:] + c.stderr[-3000:]
     collected = int(m.group(1))
-    assert collected >= 351 + 2 + 45 + 57  # + tests/test_batched_gemm_gpu.py + tests/test_exact_gpu.py
+    assert collected >= 351 + 2 + 45 + 57 + 272  # + tests/test_batched_gemm_gpu.py + tests/test_exact_gpu.py + tests/test_attention_exact_gpu.py
     r = _pytest(["-rs"], CHILD_TIME_LIMIT)  # started once: a failure is shown, not retried
     tail = r.stdout[-6000:] + r.stderr[-3000:]
     assert r.returncode == 0, tail

@@ -374,7 +374,10 @@ def _fused(dtype, seed):
 
 def test_attention_fused_projection_slices_are_passed_uncopied(monkeypatch):
     """q / k as column slices of one [B, T, 3C] projection output (what ldm_hip.transformer passes): the flash branch hands their own
-    pointers and the parent's row stride to the kernel, and returns the bits of the call on contiguous clones"""
+    pointers and the parent's row stride to the kernel, and returns the bits of the call on contiguous clones.  All T rows are keys, as
+    in self-attention: the kernels step from batch to batch by n_keys rows of k.  With fewer keys than rows (n_keys < T, two batches) the
+    wrapper has to cut and copy k, and the result is that of the call on the first n_keys rows of every batch (before, batch 1 read its
+    keys 3 rows early, and this test compared that with itself)."""
     from cremage_amd import _lib as L
     from cremage_amd import ops
     base, qkv = _fused(BF, 60)
@@ -382,10 +385,14 @@ def test_attention_fused_projection_slices_are_passed_uncopied(monkeypatch):
     q, k, vt = qkv[..., :CA], qkv[..., CA:2 * CA], _vt(BF, 61)
     spy = _Spy(L.load(), "crg_attention")
     monkeypatch.setattr(L, "load", lambda: spy)
-    got = ops.attention(q, k, vt, HEADS, NKEYS, DH ** -0.5)
+    assert T == LD
+    got = ops.attention(q, k, vt, HEADS, T, DH ** -0.5)
     (a,) = spy.calls
     assert (a[2].value, a[3], a[4].value, a[5], a[6].value, a[7]) == (q.data_ptr(), 3 * CA, k.data_ptr(), 3 * CA, vt.data_ptr(), LD)
-    ref = ops.attention(q.contiguous().clone(), k.contiguous().clone(), vt, HEADS, NKEYS, DH ** -0.5)
+    ref = ops.attention(q.contiguous().clone(), k.contiguous().clone(), vt, HEADS, T, DH ** -0.5)
+    assert same(got, ref) and torch.equal(base, before)
+    got = ops.attention(q, k, vt, HEADS, NKEYS, DH ** -0.5)
+    ref = ops.attention(q.contiguous().clone(), k[:, :NKEYS].contiguous(), vt, HEADS, NKEYS, DH ** -0.5)
     assert same(got, ref) and torch.equal(base, before)
 
 
