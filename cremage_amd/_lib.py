@@ -210,6 +210,29 @@ class ConvFramesX3Args(C.Structure):
     ]
 
 
+class FilmWarpArgs(C.Structure):
+    _fields_ = [
+        ("src", c_void_p), ("ld_src", c_int64),
+        ("flow", c_void_p), ("ld_flow", c_int64),
+        ("scale", c_void_p),
+        ("dst", c_void_p), ("ld_dst", c_int64),
+        ("hi", c_void_p), ("lo", c_void_p), ("ld_planes", c_int64),
+        ("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int),
+    ]
+
+
+class FilmActArgs(C.Structure):
+    _fields_ = [
+        ("x", c_void_p), ("ld_x", c_int64),
+        ("y", c_void_p), ("ld_y", c_int64),
+        ("hi", c_void_p), ("lo", c_void_p), ("ld_planes", c_int64),
+        ("pool", c_void_p), ("ld_pool", c_int64),
+        ("scale", c_void_p),
+        ("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int),
+        ("slope", c_float),
+    ]
+
+
 class AttnFramesArgs(C.Structure):
     _fields_ = [
         ("q", c_void_p), ("ldq", c_int64),
@@ -307,6 +330,10 @@ SIGNATURES = {
     "crg_lincomb_frames": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int]),
     "crg_conv_frames_x3": (c_int, [c_void_p, c_void_p, C.POINTER(ConvFramesX3Args)]),
     "crg_conv_frames_thin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int]),
+    "crg_film_warp": (c_int, [c_void_p, c_void_p, C.POINTER(FilmWarpArgs)]),
+    "crg_film_pool2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int]),
+    "crg_film_flow_up": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int]),
+    "crg_film_act": (c_int, [c_void_p, c_void_p, C.POINTER(FilmActArgs)]),
 }
 
 

@@ -438,6 +438,85 @@ def decode_video(first_stage, z: torch.Tensor, scale_factor: float = 0.18215, de
     return torch.cat(out, dim=0)
 
 
+def build_synthetic_film(cfg=None, device="cuda", seed: int = 1234, fill: bool = True):
+    """The FILM interpolator (cremage_amd.film_hip.Interpolator; `cfg`: its constructor arguments, default the film_net configuration) with
+    name-keyed synthetic weights.  fp32 parameters: the only class it runs in."""
+    from .film_hip import Interpolator
+    m = Interpolator(**dict(cfg or {}))
+    if fill:
+        synth_fill_(m, seed, prefix="film.")
+    return m.to(device).eval()
+
+
+def film_schedule(inter_frames: int):
+    """The order in which the reference fills the `inter_frames` frames between two given ones, as a list of model calls
+    (left slot, right slot, target slot, dt).  Slot k of 0 .. inter_frames + 1 sits at time k / (inter_frames + 1) on an fp32 time axis;
+    slots 0 and inter_frames + 1 are the given frames.  One call per open slot: among all pairs of (two neighbouring frames that exist
+    already, open slot), the pair whose slot lies closest to the midpoint between the two frames wins - the measure is the fp32 value of
+    |(t - a) / (b - a) - 1 / 2| for slot time t and frame times a, b, and of equal values the first counts, pairs of frames walked in
+    time order and open slots in time order inside each.  The call predicts the slot from those two frames at dt = (t - a) / (b - a),
+    fp32.  For three frames: the middle one, then the two quarters, each at dt = 0.5.  Pinned against what the reference's
+    `_interpolate_two_frames` really calls (tests/golden/film_schedule.npz)."""
+    import bisect
+    at = torch.linspace(0, 1, inter_frames + 2).numpy()  # the fp32 time of every slot; np.float32 scalars keep the arithmetic below in fp32
+    mid = np.float32(0.5)
+    have, missing, calls = [0, inter_frames + 1], list(range(1, inter_frames + 1)), []
+    while missing:
+        pick = None  # (measure, left, right, slot)
+        for left, right in zip(have, have[1:]):
+            for slot in missing:
+                measure = abs((at[slot] - at[left]) / (at[right] - at[left]) - mid)
+                if pick is None or measure < pick[0]:
+                    pick = (measure, left, right, slot)
+        _, left, right, slot = pick
+        calls.append((left, right, slot, float((at[slot] - at[left]) / (at[right] - at[left]))))
+        missing.remove(slot)
+        bisect.insort(have, slot)
+    return calls
+
+
+def film_pad_region(height: int, width: int, align: int):
+    """Zero padding that brings a height x width frame up to multiples of `align`, centred, with the odd pixel (if any) after the frame:
+    ((top, bottom, left, right), [y1, x1, y2, x2]) - the second is where the frame lies inside the padded one (the crop that undoes the
+    padding).  The geometry of the reference's `pad_batch`; a 30 x 50 frame at 64 gets (17, 17, 7, 7)."""
+    def around(size):
+        lack = -size % align
+        return lack // 2, lack - lack // 2
+
+    (top, bottom), (left, right) = around(height), around(width)
+    return (top, bottom, left, right), [top, left, top + height, left + width]
+
+
+@torch.no_grad()
+def interpolate_frames(model, frames: torch.Tensor, inter_frames: int = 3, *, as_uint8: bool = False, signed: bool = False) -> torch.Tensor:
+    """The Video Generator's second stage, `inference_multiple_frames(..., interpolation_frames=inter_frames, half=False)` without its
+    file and mp4 ends: frames [T, 3, H, W] fp32 in [0, 1], RGB, on the model's device -> the (T - 1) (inter_frames + 1) + 1 frames of the
+    slowed-down clip.  Every pair is padded to the model's alignment (`model.align` = 2 ** (pyramid_levels - 1) = the reference's 64)
+    with zeros as util.pad_batch does, filled in the order of `film_schedule` with one batch-1 model call per new frame - each
+    prediction clamped to [0, 1] before it may serve as a source - and cropped back; the first frame of every pair but the first is dropped.
+    `signed`: the frames are decode_video's [-1, 1] output and are mapped by clamp((x + 1) / 2, 0, 1) first (the reference goes through
+    8-bit files there; this does not round).  `as_uint8`: (x * 255).byte(), which truncates as the reference does; still RGB, [T', 3, H, W]."""
+    if frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 2:
+        raise ValueError(f"interpolate_frames: at least two [3, H, W] frames expected, got {tuple(frames.shape)}")
+    if inter_frames < 0:
+        raise ValueError(f"interpolate_frames: inter_frames = {inter_frames}")
+    frames = frames.float()
+    if signed:
+        frames = ((frames + 1.0) / 2.0).clamp(0.0, 1.0)
+    T, _, H, W = frames.shape
+    (top, bottom, left, right), (y1, x1, y2, x2) = film_pad_region(H, W, int(getattr(model, "align", 64)))
+    padded = torch.nn.functional.pad(frames, (left, right, top, bottom))
+    schedule = film_schedule(inter_frames)
+    out = []
+    for i in range(1, T):
+        slots = {0: padded[i - 1:i], inter_frames + 1: padded[i:i + 1]}
+        for lo, hi, tgt, dt in schedule:
+            slots[tgt] = model(slots[lo], slots[hi], frames.new_full((1, 1), dt)).clamp(0, 1).float()
+        out += [slots[k] for k in range(0 if i == 1 else 1, inter_frames + 2)]
+    video = torch.cat(out, dim=0)[:, :, y1:y2, x1:x2]
+    return (video * 255).byte() if as_uint8 else video.contiguous()
+
+
 @torch.no_grad()
 def img2vid_latents(engine, c: dict, uc: dict, *, num_frames: int, steps: int = 30, min_scale: float = 1.0, max_scale: float = 2.5,
                     height: int = 576, width: int = 1024, x0: Optional[torch.Tensor] = None, seed: int = 0,

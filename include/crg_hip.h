@@ -783,6 +783,47 @@ int crg_conv_frames_x3(crg_ctx* ctx, void* stream, const crg_conv_frames_x3_args
 int crg_conv_frames_thin(crg_ctx* ctx, void* stream, const void* x, const float* w, const float* bias, void* y, int b, int T, int S, int C,
                          int dtype);
 
+/* ---- data movements of the FILM frame interpolator (film.hip) --------------------------------------------------------------------------
+ * Channels-last fp32 rows: pixel (n, y, x) of an [N, H, W] tensor is row (n*H + y)*W + x, its channels consecutive, rows `ld` ELEMENTS
+ * apart.  A pointer carries its channel offset already, so a destination may be a column slice [off, off + C) of a wider buffer (the
+ * reference's torch.cat as a write); a kernel never touches the other columns.  Pointers need their element's alignment only; 16-byte
+ * accesses are used where pointers, strides and C allow.  Sources and destinations of one call must not overlap, except crg_film_act's
+ * y == x.  Profile slot: CRG_K_ELEMENTWISE.
+ *
+ * crg_film_warp: backward warp (frame_interpolation_pytorch util.warp).  dst[n,y,x,c] = bilinear(src[n], x + s*flow[n,y,x,0],
+ *   y + s*flow[n,y,x,1])[c], c < C: the position is clamped to [0, W-1] x [0, H-1] (grid_sample padding_mode 'border', align_corners
+ *   False), s = scale[n] (fp32 [N]) or 1 for NULL.  Up to 64 lanes share a pixel; each of them reads the pixel's flow (one broadcast access)
+ *   and computes the four weights once, then walks its share of the C channels - the weights are per lane, not per channel.  An integral
+ *   position returns the source pixel bit for bit.  dst fp32 and / or the half-type planes hi = half(v), lo = half(v - hi), rows ld_planes apart.
+ * crg_film_pool2: F.avg_pool2d(x, 2, 2): dst [N, H/2, W/2] (floor), ((a + b) + c + d) * 0.25 in reading order.
+ * crg_film_flow_up: dst = residual + F.interpolate(2*v, size = (2h, 2w), mode 'bilinear') on 2 channels; v [N, h, w], residual (or NULL)
+ *   and dst [N, 2h, 2w].
+ * crg_film_act: y = scale[n] * (x >= 0 ? x : slope*x) of x [N, H, W] x C (scale fp32 [N], or NULL: no product; slope 1 makes it a scaled
+ *   copy into a slice, which is how multiply_pyramid's dt / 1 - dt reach the fusion's input), as fp32 (y, may be x itself), as planes (hi, lo) and / or as its 2 x 2 mean
+ *   (pool [N, H/2, W/2], floor) - any non-empty subset, one pass over x. */
+typedef struct {
+  const float* src; int64_t ld_src;
+  const float* flow; int64_t ld_flow;
+  const float* scale;
+  float* dst; int64_t ld_dst;
+  void* hi; void* lo; int64_t ld_planes;
+  int N, H, W, C;
+} crg_film_warp_args;
+int crg_film_warp(crg_ctx* ctx, void* stream, const crg_film_warp_args* args);
+int crg_film_pool2(crg_ctx* ctx, void* stream, const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int N, int H, int W, int C);
+int crg_film_flow_up(crg_ctx* ctx, void* stream, const float* v, int64_t ld_v, const float* residual, int64_t ld_res, float* dst, int64_t ld_dst,
+                     int N, int h, int w);
+typedef struct {
+  const float* x; int64_t ld_x;
+  float* y; int64_t ld_y;
+  void* hi; void* lo; int64_t ld_planes;
+  float* pool; int64_t ld_pool;
+  const float* scale;
+  int N, H, W, C;
+  float slope;
+} crg_film_act_args;
+int crg_film_act(crg_ctx* ctx, void* stream, const crg_film_act_args* args);
+
 #ifdef __cplusplus
 }
 #endif
