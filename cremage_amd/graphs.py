@@ -25,7 +25,7 @@ Correctness rules enforced here:
     although no parameter changed.  load_state_dict (in-place copy -> version), `.to()` / `.half()` (new storage ->
     data_ptr), LoRA swaps and cache clears therefore re-capture instead of replaying against stale or freed weight images;
     `invalidate()` remains for writes through `.data`, which no counter sees;
-  * module-level knobs of `ops` that pick a kernel per call (`ATTN_X3_FLASH` / CRG_ATTN_X3, like `FF_MX8`'s module default) are read
+  * the knobs of `cremage_amd.knobs` that pick a kernel per call (`ATTN_X3_FLASH` / CRG_ATTN_X3, like `FF_MX8`'s module default) are read
     when the forward RUNS, i.e. at capture time: a graph replays the route it captured, and the knob is not part of the key.
     They are process settings read from the environment at import; code that flips one between calls calls `invalidate()`;
   * a failed capture RAISES (`strict=True`, the default): the caller asked for replay, and a silent switch to eager

@@ -25,13 +25,8 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import knobs, ops
 from .nn import Conv2d, Linear, Normalize, zero_module
-
-
-import os
-
-_SELF_QKV = os.environ.get("CRG_SELF_QKV", "1") != "0"  # dev knob: 0 = self-attention as fused Q|K GEMM + transposed-V GEMM (round-1 form)
 
 
 def exists(v):
@@ -121,12 +116,12 @@ class FeedForward(nn.Module):
     def __init__(self, dim, dim_out=None, mult=4, glu=False, dropout=0., lora_ranks: List[int] = None,
                  lora_weights: List[float] = None, precision: Optional[str] = None):
         """`precision` (not in the reference's signature): None = the input's own precision, as ever; "mx8" = both GEMMs on block-scaled
-        e4m3 operands (ops.linear_mx8) for half-type inputs.  None becomes "mx8" under CRG_FF_MX8=1 (ops.FF_MX8);
+        e4m3 operands (ops.linear_mx8) for half-type inputs.  None becomes "mx8" under CRG_FF_MX8=1 (knobs.FF_MX8);
         cremage_amd.set_ff_precision switches a whole model."""
         super().__init__()
         if precision not in (None, "mx8"):
             raise ValueError(f"FeedForward: precision {precision!r} (None or 'mx8')")
-        self.precision = precision or ("mx8" if ops.FF_MX8 else None)
+        self.precision = precision or ("mx8" if knobs.FF_MX8 else None)
         self.lora_ranks = lora_ranks if lora_ranks is not None else []
         self.lora_weights = lora_weights if lora_weights is not None else [1.0] * len(self.lora_ranks)
         inner_dim = int(dim * mult)
@@ -242,12 +237,12 @@ class CrossAttention(nn.Module):
             if self.ipa_num_tokens > 0:
                 raise NotImplementedError("ipa_num_tokens > 0 needs a context (attention.py:623-627)")
             wqkv = self._stack(wq, wk, wv) if fused else None
-            if fused and _SELF_QKV and ln is not None and not ops.ln_epi_ok(x, wqkv) and ops.ln_linear_ok(x, wqkv, transposed_from=2 * c):
+            if fused and knobs.SELF_QKV and ln is not None and not ops.ln_epi_ok(x, wqkv) and ops.ln_linear_ok(x, wqkv, transposed_from=2 * c):
                 # 64x64 level: LayerNorm + Q | K | V in ONE launch whose V third is written transposed, so that the 4096-token
                 # self-attention runs on the transposed-V flash kernel (the row-major-V variant is 10-20 % slower there)
                 qk, vt = ops.ln_linear(x, ln.weight, ln.bias, ln.eps, wqkv, transposed_from=2 * c)
                 return out_proj(ops.attention(qk[..., :c], qk[..., c:], vt, self.heads, x.shape[1], self.scale))
-            if fused and _SELF_QKV and x.dim() == 3 and x.shape[1] % 64 == 0 and (c // self.heads) in (40, 64, 80) \
+            if fused and knobs.SELF_QKV and x.dim() == 3 and x.shape[1] % 64 == 0 and (c // self.heads) in (40, 64, 80) \
                     and ops.linear_transposed_ok(x, wqkv, 2 * c):
                 # head dims with an LDS-DMA / pipelined attention kernel (they stage V^T): the V third of the fused projection comes
                 # out transposed from the GEMM's own epilogue (LayerNorm: as an epilogue correction of the same launch when x carries
@@ -255,7 +250,7 @@ class CrossAttention(nn.Module):
                 # SDXL 4 x 4096, d 64: 256 -> 205 us (tools/attn_vt_probe.py)
                 qk, vt = project(wqkv, transposed_from=2 * c)
                 return out_proj(ops.attention(qk[..., :c], qk[..., c:], vt, self.heads, x.shape[1], self.scale))
-            if fused and _SELF_QKV:
+            if fused and knobs.SELF_QKV:
                 # self-attention: the three projections share their input -> ONE GEMM, q / k / v are column slices of its output
                 qkv = project(wqkv)
                 return out_proj(ops.attention_rows_v(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:], self.heads, self.scale))

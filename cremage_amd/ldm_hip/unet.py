@@ -24,7 +24,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import knobs, ops
 from .nn import Conv2d, Linear, SiLU, conv_nd, linear, normalization, timestep_embedding, zero_module
 from .transformer import SpatialTransformer, exists
 
@@ -380,7 +380,7 @@ class UNetModel(nn.Module):
         split then needs the same promise on it as well (ops.mark_cfg_dup(c_concat)), else the whole batch runs."""
         if c_concat is not None and not getattr(c_concat, "_crg_cfg_dup", False):
             cfg_dup = False
-        split = self._cfg_split_index() if (cfg_dup and ops.CFG_SHARE and x.shape[0] % 2 == 0 and context is not None) else None
+        split = self._cfg_split_index() if (cfg_dup and knobs.CFG_SHARE and x.shape[0] % 2 == 0 and context is not None) else None
         hs = []
         if split is None:
             h = ops.nchw_to_nhwc(x, cdt, c_concat)

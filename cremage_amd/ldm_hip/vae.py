@@ -82,7 +82,7 @@ class ResnetBlock(nn.Module):
     def forward(self, x, temb=None, gn_stats: bool = True):
         """`gn_stats` False: the fp32-class conv2 emits no GroupNorm statistics (a caller whose next layer does not read them)"""
         if ops.mx_conv_ok(x, self.conv1.weight) and self.conv2.in_channels % 64 == 0 and self.conv2.out_channels % 4 == 0:
-            # opt-in (CRG_VAE_MX=1): the same block on MX planes (CRG_PREC_F16MX: one fp16 pass + fp8 cross terms), see ops.VAE_MX
+            # opt-in (CRG_VAE_MX=1): the same block on MX planes (CRG_PREC_F16MX: one fp16 pass + fp8 cross terms), see knobs.VAE_MX
             a16, a8 = self.norm1(x, silu=True, split="mx")
             h = self.conv1(a16, x_mx=a8, gn_stats=True)
             a16, a8 = self.norm2(h, silu=True, split="mx")

@@ -21,7 +21,7 @@ import functools
 import numpy as np
 import torch
 
-from . import ops
+from . import knobs, ops
 
 
 def append_zero(x):
@@ -258,7 +258,7 @@ def with_time_rows(unet, t_rep):
     (`UNetModel.time_rows` for the whole table, `ops.attach_time_rows` per row) when `unet` offers it; plain rows otherwise."""
     rows = [t_rep[i] for i in range(t_rep.shape[0])]
     f = getattr(unet, "time_rows", None)
-    if f is not None and t_rep.is_cuda and ops.TIME_ROWS:
+    if f is not None and t_rep.is_cuda and knobs.TIME_ROWS:
         tr = f(t_rep)
         for i, r in enumerate(rows):
             ops.attach_time_rows(r, tr[i], unet)

@@ -21,12 +21,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import knobs, ops
 from .sampler_plan import (EDMDiscretization, _entry, _sigma_fn, _t_fn, append_zero, doubled_input, plan_dpmpp_2m,  # noqa: F401
                            plan_dpmpp_2s_a, plan_draws, plan_heun, plan_lms, run_plan, with_time_rows)
-
-# dev knob: 0 = the fused sampler steps compute the CompVis wrapper's scalings and timestep per step (round 2) instead of once per run
-STEP_TABLES = __import__("os").environ.get("CRG_SAMPLER_TABLES", "1") != "0"
 
 
 def append_dims(x, target_dims):
@@ -293,7 +290,7 @@ def sample_euler(model, x, sigmas, extra_args=None, callback=None, disable=None,
     tables = None
     if fused:
         x = x.clone().contiguous()  # updated in place by the fused step
-        if STEP_TABLES and s_churn == 0. and len(sigmas) > 1:  # sigma_hat == sigma on every step: the wrapper's per-step scalars from one vectorised pass
+        if knobs.STEP_TABLES and s_churn == 0. and len(sigmas) > 1:  # sigma_hat == sigma on every step: the wrapper's per-step scalars from one vectorised pass
             tables = model.step_tables(sigmas[:-1], x.shape[0])
     for i in range(len(sigmas) - 1):
         gamma = min(s_churn / (len(sigmas) - 1), 2 ** 0.5 - 1) if s_tmin <= sh[i].item() <= s_tmax else 0.
@@ -325,7 +322,7 @@ def sample_euler_ancestral(model, x, sigmas, extra_args=None, callback=None, dis
     fused = callback is None and not extra_args and getattr(model, "fused_step_ok", lambda _x: False)(x)
     if fused:
         x = x.clone().contiguous()  # updated in place by the fused step
-        tables = STEP_TABLES and len(sigmas) > 1
+        tables = knobs.STEP_TABLES and len(sigmas) > 1
         if tables:
             c_in_all, t_rep = model.step_tables(sigmas[:-1], x.shape[0])
     for i in range(len(sigmas) - 1):

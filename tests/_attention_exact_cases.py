@@ -68,7 +68,7 @@ class Case:
     G: int = 0                    # uni: the period
     knobs: Tuple = ()             # ((env name, value), ...): runs in a child process of its own (tests/_attn_knob_run.py)
     f32: bool = False             # unfused: fp32 tensors (the fp32-class GEMMs) instead of the half type
-    budget: int = 0               # unfused: ops.SCORE_BUDGET_BYTES for the call, so that the queries split into chunks with a tail
+    budget: int = 0               # unfused: ops.knobs.SCORE_BUDGET_BYTES for the call, so that the queries split into chunks with a tail
 
     @property
     def vrm(self):
@@ -304,12 +304,12 @@ def run(case, ops, t):
         return ops.attention(t["q"], t["k"], t["vt"], case.H, case.Nk, SCALE)
     if case.entry == "x3":
         return ops.attention(t["q"], t["k"], t["vt"], case.H, case.Nk, SCALE, flash=True)
-    old = ops.SCORE_BUDGET_BYTES
-    ops.SCORE_BUDGET_BYTES = case.budget
+    old = ops.knobs.SCORE_BUDGET_BYTES
+    ops.knobs.SCORE_BUDGET_BYTES = case.budget
     try:
         return ops.attention(t["q"], t["k"], t["vt"], case.H, case.Nk, SCALE, flash=False)
     finally:
-        ops.SCORE_BUDGET_BYTES = old
+        ops.knobs.SCORE_BUDGET_BYTES = old
 
 
 # ------------------------------------------------------------------------------------------ criteria

@@ -29,10 +29,20 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layouts_match_header():
-    """field order of the ctypes structures == field order of the C structs"""
+    """field order of EVERY ctypes structure of the binding == field order of the C struct it mirrors, and no structure is left unpaired"""
+    import ctypes
     from cremage_amd import _lib
     header = open(os.path.join(REPO, "include", "crg_hip.h")).read()
-    for cname, cls in [("crg_gemm_args", _lib.GemmArgs), ("crg_conv_args", _lib.ConvArgs), ("crg_route", _lib.Route)]:
+    pairs = {"crg_profile": _lib.Profile, "crg_lngemm_args": _lib.LnGemmArgs, "crg_gemm_args": _lib.GemmArgs, "crg_conv_args": _lib.ConvArgs,
+             "crg_route": _lib.Route, "crg_sampler_step_args": _lib.SamplerStepArgs, "crg_kstep_args": _lib.KStepArgs,
+             "crg_resample_args": _lib.ResampleArgs, "crg_poisson_args": _lib.PoissonArgs, "crg_blend_args": _lib.BlendArgs,
+             "crg_mx8gemm_args": _lib.Mx8GemmArgs, "crg_attn_x3_args": _lib.AttnX3Args, "crg_conv_frames_args": _lib.ConvFramesArgs,
+             "crg_attn_frames_args": _lib.AttnFramesArgs, "crg_conv_frames_x3_args": _lib.ConvFramesX3Args,
+             "crg_film_warp_args": _lib.FilmWarpArgs, "crg_film_act_args": _lib.FilmActArgs}
+    mirrors = {v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert mirrors == set(pairs.values()), sorted(c.__name__ for c in mirrors ^ set(pairs.values()))
+    assert sorted(pairs) == sorted(re.findall(r"^\} (crg_\w+);", header, re.M))  # ... and no struct of the header without its mirror
+    for cname, cls in pairs.items():
         body = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\} " + cname + ";", header, re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         names = []
@@ -41,8 +51,8 @@ def test_struct_layouts_match_header():
             if not decl:
                 continue
             parts = [p.strip() for p in decl.split(",")]
-            names.append(re.findall(r"(\w+)(?:\[\d+\])?$", parts[0])[0])   # (`int mx_log2[4]`: an array field counts once)
-            names += [re.findall(r"(\w+)(?:\[\d+\])?$", p)[0] for p in parts[1:]]
+            names.append(re.findall(r"(\w+)(?:\[\w+\])?$", parts[0])[0])   # (`int mx_log2[4]`, `double ms[CRG_K_SLOTS]`: an array field counts once)
+            names += [re.findall(r"(\w+)(?:\[\w+\])?$", p)[0] for p in parts[1:]]
         assert names == [f[0] for f in cls._fields_], (cname, names)
 
 

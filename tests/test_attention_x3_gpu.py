@@ -209,7 +209,7 @@ def test_domain_errors(monkeypatch):
     a = L.AttnX3Args(q=buf, ldq=520, k=buf, ldk=520, vt=buf, ldvt=8, o=buf, ldo=520, B=1, H=1, Nq=8, Nk=8, Dh=520, scale=1.0)
     assert L.load().crg_attention_x3(L.ctx(0), None, ctypes.byref(a)) == -22
     # flash=None with the knob unset: the unfused branch, the new entry point is not called
-    monkeypatch.setattr(ops, "ATTN_X3_FLASH", False)
+    monkeypatch.setattr(ops.knobs, "ATTN_X3_FLASH", False)
     qq, kk, vt = rnd(1, 24, 64, seed=487).to(_dev()), rnd(1, 16, 64, seed=488).to(_dev()), _vt_of(rnd(1, 16, 64, seed=489)).to(_dev())
     assert ops.attention_x3_ok(qq, kk, vt, 2, 16)
     unfused = ops.attention(qq, kk, vt, 2, 16, 0.2, flash=False)
@@ -220,6 +220,6 @@ def test_domain_errors(monkeypatch):
     monkeypatch.setattr(L, "load", lambda: spy)
     assert torch.equal(ops.attention(qq, kk, vt, 2, 16, 0.2), unfused) and not spy.calls
     # ... and with it set, flash=None takes the kernel
-    monkeypatch.setattr(ops, "ATTN_X3_FLASH", True)
+    monkeypatch.setattr(ops.knobs, "ATTN_X3_FLASH", True)
     with pytest.raises(AssertionError, match="knob unset"):
         ops.attention(qq, kk, vt, 2, 16, 0.2)

@@ -1,4 +1,4 @@
-"""The modules that call `ops.attention` on fp32 tensors, with the fp32-class flash kernel switched on (ops.ATTN_X3_FLASH, what
+"""The modules that call `ops.attention` on fp32 tensors, with the fp32-class flash kernel switched on (ops.knobs.ATTN_X3_FLASH, what
 CRG_ATTN_X3=1 sets): the goldens and bounds these fixtures carry in tests/test_hip_models.py, unchanged."""
 import pytest
 import torch
@@ -16,7 +16,7 @@ def x3(monkeypatch):
     """knob on; counts the launches of the new kernel, so that a test cannot pass on the unfused branch"""
     from cremage_amd import _lib as L
     from cremage_amd import ops
-    monkeypatch.setattr(ops, "ATTN_X3_FLASH", True)
+    monkeypatch.setattr(ops.knobs, "ATTN_X3_FLASH", True)
     lib, calls = L.load(), []
 
     class Counting:

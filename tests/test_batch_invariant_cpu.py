@@ -113,11 +113,12 @@ def test_linear_wrappers_pass_rows_per_sample(monkeypatch):
     """linear / conv1x1 / linear_transposed hand crg_gemm the per-sample rows (no launch: crg_gemm is intercepted)"""
     from cremage_amd import _lib, ops
     seen = []
-    monkeypatch.setattr(ops, "_gemm", lambda h, **kw: seen.append(kw))
-    monkeypatch.setattr(ops, "_need_cuda", lambda *ts: None)
-    monkeypatch.setattr(ops, "_h", lambda t: None)
-    monkeypatch.setattr(ops, "packed_weight", lambda w, kind, split: (w, w if split else None))
-    monkeypatch.setattr(ops, "f32_vec", lambda v: v)
+    G = ops.gemm  # the module of linear / linear_transposed, where they look these names up (conv1x1 goes through its linear)
+    monkeypatch.setattr(G, "_gemm", lambda h, **kw: seen.append(kw))
+    monkeypatch.setattr(G, "_need_cuda", lambda *ts: None)
+    monkeypatch.setattr(G, "_h", lambda t: None)
+    monkeypatch.setattr(G, "packed_weight", lambda w, kind, split: (w, w if split else None))
+    monkeypatch.setattr(G, "f32_vec", lambda v: v)
     w = torch.zeros(64, 32)
     ops.linear(torch.zeros(3, 50, 32, dtype=ops.HALF), w)
     ops.linear(torch.zeros(7, 32, dtype=ops.HALF), w)

@@ -227,7 +227,7 @@ def test_unfused_attention_batched(dtype, B, heads, d, Nq, Nk, late_key, chunk, 
     from cremage_amd import ops
     assert dtype == F32 or d > 160  # the unfused branch of ops.attention
     if chunk:
-        monkeypatch.setattr(ops, "SCORE_BUDGET_BYTES", 4 * heads * ((Nk + 7) // 8 * 8) * chunk)
+        monkeypatch.setattr(ops.knobs, "SCORE_BUDGET_BYTES", 4 * heads * ((Nk + 7) // 8 * 8) * chunk)
     qq, kk, vv, vt = _attn_inputs(dtype, B, heads, d, Nq, Nk, late_key)
     ref = _attn_ref64(q(qq, dtype), q(kk, dtype), q(vv, dtype), heads, d ** -0.5)
     with ops.profile() as pr:

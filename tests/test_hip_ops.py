@@ -181,7 +181,7 @@ def test_layernorm_as_gemm_epilogue(M, K, N, act, vt, monkeypatch):
     LayerNorm in fp32 on the very bf16 rows the producer stored; rows with a mean of six standard deviations exercise the
     cancellation mean * colsum; transposed V range, GEGLU (both kernels), every tile configuration."""
     from cremage_amd import ops
-    monkeypatch.setattr(ops, "LN_EPI_320", 2)
+    monkeypatch.setattr(ops.knobs, "LN_EPI_320", 2)
     dev = _dev()
     mean = 0.0 if (M, N) in ((8192, 640), (512, 1280)) else 6.0  # (row means of six standard deviations: the cancellation mean * colsum)
     T = 1024 if M % 1024 == 0 else M
@@ -881,7 +881,7 @@ def test_gn_tile_partials():
     batch-doubled copy (ops.dup_batch) equals the reference."""
     from cremage_amd import ops
     dev = _dev()
-    if not ops.GN_TILE:
+    if not ops.knobs.GN_TILE:
         pytest.skip("CRG_GN_TILE=0")
     N, hw = 8, 64  # the UNet's own 64x64-level shapes (one 256-pixel tile per CU and more)
 
@@ -1147,7 +1147,7 @@ def test_unfused_attention_query_chunks_with_tail(dtype, heads, d, monkeypatch):
     from cremage_amd import ops
     C, Nq, Nk = heads * d, 150, 77
     kp = (Nk + 7) // 8 * 8
-    monkeypatch.setattr(ops, "SCORE_BUDGET_BYTES", 4 * heads * kp * 64)
+    monkeypatch.setattr(ops.knobs, "SCORE_BUDGET_BYTES", 4 * heads * kp * 64)
     qq, kk, vv = rnd(2, Nq, C, seed=86), rnd(2, Nk, C, seed=87), rnd(2, Nk, C, seed=88)
     vt = F.pad(vv.transpose(1, 2), (0, (-Nk) % 8)).contiguous()
     ref = attn_ref(q(qq, dtype), q(kk, dtype), q(vv, dtype), heads, d ** -0.5)

@@ -113,7 +113,7 @@ def test_set_ff_precision_switches_every_feed_forward():
     from cremage_amd.ldm_hip.transformer import BasicTransformerBlock, FeedForward
     import pytest
     m = torch.nn.Sequential(BasicTransformerBlock(64, 2, 32, context_dim=64), BasicTransformerBlock(64, 2, 32, context_dim=64))
-    assert all(f.precision is None for f in m.modules() if isinstance(f, FeedForward)) or ops.FF_MX8
+    assert all(f.precision is None for f in m.modules() if isinstance(f, FeedForward)) or ops.knobs.FF_MX8
     assert cremage_amd.set_ff_precision(m, "mx8") == 2
     assert all(f.precision == "mx8" for f in m.modules() if isinstance(f, FeedForward))
     assert cremage_amd.set_ff_precision(m, None) == 2

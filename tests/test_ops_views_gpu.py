@@ -13,7 +13,7 @@ channel range of an image in either layout, every second element of a vector), v
 (NCHW where channels-last is expected and the reverse; tokens, matrices and vt: the transpose of a transposed tensor), v4 = an expanded
 dim (stride 0).  Every view keeps a 16-byte-aligned data_ptr().
 
-Which case fails without which fix of cremage_amd/ops.py:
+Which case fails without which fix of cremage_amd/ops/:
   attention (vt made contiguous)        : test_views[attention-*-vt-v2], [attention-*-vt-v3] (both dtypes: the flash and the unfused branch)
   attention (argument checks)           : test_attention_argument_errors[*], test_attention_unfused_branch_needs_the_pad_columns_of_vt
                                           (written against the checked wrapper: n_keys beyond k or vt would read past a buffer on an

@@ -84,15 +84,15 @@ def decode(a):
 
     def arm(on):
         def f():
-            ops.ATTN_X3_FLASH = on
+            ops.knobs.ATTN_X3_FLASH = on
             return m.decode(z)
         return f
-    keep = ops.ATTN_X3_FLASH
+    keep = ops.knobs.ATTN_X3_FLASH
     try:
         with torch.no_grad():
             med, rounds = _pairs({"knob_off": arm(False), "knob_on": arm(True)})
     finally:
-        ops.ATTN_X3_FLASH = keep
+        ops.knobs.ATTN_X3_FLASH = keep
     print(json.dumps({"figure": "sd15_vae_decode_512_ms", "knob_off_ms": round(med["knob_off"], 3), "knob_on_ms": round(med["knob_on"], 3),
                       "on_over_off": round(med["knob_on"] / med["knob_off"], 4),
                       "rounds_ms": {k: [round(t, 3) for t in v] for k, v in rounds.items()}}), flush=True)

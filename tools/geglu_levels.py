@@ -7,7 +7,7 @@ from cremage_amd import ops
 from tools.gt import graph_us
 dev = "cuda:0"
 torch.manual_seed(0)
-ops.LN_EPI_320 = 2
+ops.knobs.LN_EPI_320 = 2
 out = []
 for (T, C) in [(4096, 320), (1024, 640), (256, 1280), (64, 1280)]:
     x0 = torch.randn(8, T, C, device=dev).to(torch.bfloat16)

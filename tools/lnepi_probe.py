@@ -7,7 +7,7 @@ from cremage_amd import ops
 from tools.gt import graph_us
 dev = "cuda:0"
 torch.manual_seed(0)
-ops.LN_EPI_320 = 2
+ops.knobs.LN_EPI_320 = 2
 B = int(os.environ.get("PROBE_B", "8"))
 tot = {"sep": 0.0, "epi": 0.0}
 for (T, C, cnt) in [(4096, 320, 5), (1024, 640, 5), (256, 1280, 5), (64, 1280, 1)]:
