@@ -17,7 +17,7 @@ BF16, F32, F16 = 0, 1, 2
 PREC_BF16, PREC_BF16X3, PREC_F16MX = 0, 1, 2
 EPI_NONE, EPI_SILU, EPI_GEGLU = 0, 1, 2
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
-PACK_LINEAR, PACK_CONV, PACK_GEGLU, PACK_CONV_UP2 = 0, 1, 2, 3
+PACK_LINEAR, PACK_CONV, PACK_GEGLU, PACK_CONV_UP2, PACK_CONVT_UP2 = 0, 1, 2, 3, 4
 K_SLOTS = 17  # enum crg_kernel_slot
 SLOT_NAMES = ["gemm_w1", "gemm_w4", "gemm_w5", "gemm_x3", "conv_w1", "conv_w4", "conv_w5", "conv_x3", "splitk_reduce", "attention",
               "gn_stats", "gn_apply", "layernorm", "elementwise", "conv_small", "softmax", "lngemm"]
@@ -245,7 +245,7 @@ class AttnFramesArgs(C.Structure):
     ]
 
 
-ROUTE_KERNELS = ["none", "glds", "rowhalo", "conv_pp", "gemm_ring", "gemm_reg", "planes"]  # enum crg_route_kernel
+ROUTE_KERNELS = ["none", "glds", "rowhalo", "conv_pp", "gemm_ring", "gemm_reg", "planes", "convt"]  # enum crg_route_kernel
 ROUTE_REDUCES = ["none", "plain", "stats", "rows", "gn"]  # enum crg_route_reduce
 
 
@@ -334,6 +334,9 @@ SIGNATURES = {
     "crg_film_pool2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int]),
     "crg_film_flow_up": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int]),
     "crg_film_act": (c_int, [c_void_p, c_void_p, C.POINTER(FilmActArgs)]),
+    "crg_conv_transpose2d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "crg_groupnorm_add_act": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int]),
 }
 
 

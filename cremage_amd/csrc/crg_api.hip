@@ -210,6 +210,32 @@ __global__ void pack_up2_kernel(const ST* __restrict__ src, bf16* __restrict__ h
   }
 }
 
+// CRG_PACK_CONVT_UP2: [Cin][Cout][4][4] -> the parity image [parity a b][Cout][K = 4 Cin] of ConvTranspose2d(4, 2, 1): tap (u, v) of slab
+// (a, b) is W[ci][co][3 - a - 2u][3 - b - 2v] - selected, not summed.  K order [Cin / 64][u][v][64] when Cin % 64 == 0, else [u][v][Cin].
+template <typename ST>
+__global__ void pack_convt_kernel(const ST* __restrict__ src, bf16* __restrict__ hi, bf16* __restrict__ lo, int n_out, int n_in, long total) {
+  const bool cm = n_in % 64 == 0;
+  for (long d = (long)blockIdx.x * blockDim.x + threadIdx.x; d < total; d += (long)gridDim.x * blockDim.x) {
+    const int kk = 4 * n_in;
+    const long row = d / kk;
+    const int k = (int)(d - row * kk);
+    const int par = (int)(row / n_out), o = (int)(row - (long)par * n_out);
+    int tap, ci;
+    if (cm) {
+      tap = (k >> 6) & 3;
+      ci = (k >> 8) * 64 + (k & 63);
+    } else {
+      tap = k / n_in;
+      ci = k - tap * n_in;
+    }
+    const int a = par >> 1, b = par & 1, u = tap >> 1, v = tap & 1;
+    const float f = (float)src[(((long)ci * n_out + o) * 4 + (3 - a - 2 * u)) * 4 + (3 - b - 2 * v)];
+    const bf16 h = (bf16)f;
+    hi[d] = h;
+    if (lo) lo[d] = (bf16)(f - (float)h);
+  }
+}
+
 __global__ void pack_geglu_bias_kernel(const float* __restrict__ src, float* __restrict__ dst, int n2) {
   const int o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= n2) return;
@@ -321,6 +347,18 @@ extern "C" int crg_pack_weight(crg_ctx* ctx, void* stream, const void* src, int 
     if (src_dtype == CRG_F32) hipLaunchKernelGGL(pack_up2_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
     else if (src_dtype == CRG_BF16) hipLaunchKernelGGL(pack_up2_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
     else if (src_dtype == CRG_F16) hipLaunchKernelGGL(pack_up2_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else return crg_fail(ctx, -22, "pack_weight: unsupported source dtype %d", src_dtype);
+    CRG_CHECK_LAUNCH(ctx, "pack_weight");
+    return 0;
+  }
+  if (kind == CRG_PACK_CONVT_UP2) {
+    CRG_REQUIRE(ctx, ksize == 4 && n_in % 8 == 0, "pack_weight: the transposed-conv parity image takes 4x4 weights with Cin %% 8 == 0 (ksize %d, Cin %d)", ksize, n_in);
+    const long total = 16L * n_out * n_in;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == CRG_F32) hipLaunchKernelGGL(pack_convt_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else if (src_dtype == CRG_BF16) hipLaunchKernelGGL(pack_convt_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
+    else if (src_dtype == CRG_F16) hipLaunchKernelGGL(pack_convt_kernel<_Float16>, dim3(grid), dim3(256), 0, st, (const _Float16*)src, (bf16*)dst_hi, (bf16*)dst_lo, n_out, n_in, total);
     else return crg_fail(ctx, -22, "pack_weight: unsupported source dtype %d", src_dtype);
     CRG_CHECK_LAUNCH(ctx, "pack_weight");
     return 0;

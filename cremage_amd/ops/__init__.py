@@ -30,14 +30,15 @@ from .norms import group_norm, layer_norm, softmax_rows_
 from .packing import MX_X_LOG2, packed_geglu_bias, packed_ln_weight, packed_weight, packed_weight_mx, split_mx
 from .side_channels import (GN_STATS_MIN_HW, _gn_rows_of, _gn_stats_of, attach_time_rows, dup_batch, ln_epi_ok, ln_epi_wanted,  # noqa: F401
                             mark_cfg_dup, row_stats_parts, time_rows_of)
+from .unblur import conv_transpose2d, group_norm_add_act
 from .steps import KSTEP_KINDS, STEP_KINDS, axpby_, cfg_ddim_step_, cfg_dpmpp2m_step_, cfg_euler_step_, cfg_kstep_, cfg_sampler_step_, silu, timestep_embedding
 
 __all__ = [
     "BLEND_GRAY", "GN_STATS_MIN_HW", "HALF", "KSTEP_KINDS", "MAX_FRAMES", "MX_X_LOG2", "RESAMPLE_BITS", "STEP_KINDS", "TensorKeyedCache", "add_frames",
     "affine_cast", "attach_time_rows", "attention", "attention_frames", "attention_rows_v", "attention_x3_ok", "avg_pool2", "axpby_", "bilinear_tables",
     "blend_frames", "blur_blend_u8", "cfg_ddim_step_", "cfg_dpmpp2m_step_", "cfg_euler_step_", "cfg_kstep_", "cfg_sampler_step_", "clear_weight_cache",
-    "conv1x1", "conv2d", "conv_frames", "conv_frames_thin", "conv_frames_x3", "dequant_mx8_host", "dup_batch", "empty_image", "f32_vec", "ff_mx8_ok",
-    "flow_up2_add", "frames_weight", "group_norm", "image_of", "image_of_stats", "lanczos_tables", "last_route", "layer_norm", "leaky_split",
+    "conv1x1", "conv2d", "conv_transpose2d", "conv_frames", "conv_frames_thin", "conv_frames_x3", "dequant_mx8_host", "dup_batch", "empty_image", "f32_vec", "ff_mx8_ok",
+    "flow_up2_add", "frames_weight", "group_norm", "group_norm_add_act", "image_of", "image_of_stats", "lanczos_tables", "last_route", "layer_norm", "leaky_split",
     "lincomb_frames", "linear", "linear_mx8", "linear_mx8_host", "linear_transposed", "linear_transposed_ok", "ln_epi_ok", "ln_epi_wanted", "ln_linear",
     "ln_linear_auto", "ln_linear_ok", "mark_cfg_dup", "mx_conv_ok", "nchw_to_nhwc", "nhwc_to_nchw", "packed_geglu_bias", "packed_ln_weight",
     "packed_weight", "packed_weight_mx", "packed_weight_mx8", "poisson_clone", "poisson_tables", "profile", "quant_mx8", "quant_mx8_host",

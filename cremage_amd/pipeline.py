@@ -448,6 +448,32 @@ def build_synthetic_film(cfg=None, device="cuda", seed: int = 1234, fill: bool =
     return m.to(device).eval()
 
 
+def build_synthetic_unblur(device="cuda", seed: int = 1234, fill: bool = True):
+    """Cremage's face unblur / colorize network (cremage_amd.unblur_hip.UnblurCremageModelV6, 620 M parameters) built on the device and
+    filled there module by module with name-keyed synthetic weights.  fp32 parameters: the only class it runs in."""
+    from .unblur_hip import UnblurCremageModelV6
+    with torch.device(device):
+        m = UnblurCremageModelV6()
+    if fill:
+        synth_fill_(m, seed, prefix="unblur.")
+    return m.eval()
+
+
+@torch.no_grad()
+def unblur_faces(model, image, landmarks, *, glue: str = "host"):
+    """The Face Fixer's "Unblur face" / "Colorize face" on an image whose faces were detected elsewhere (face_unblur.py:227-271): per face
+    the five landmarks give the similarity transform onto the 256 x 256 template, the aligned face goes through `model` (the unblur or
+    the colorize weights) and is warped back and pasted under its eroded mask.  image: uint8 [H, W, 3] (numpy array or tensor); landmarks:
+    [faces, 5, 2].  glue "host": numpy on the host (postprocess.unblur_faces), returns a numpy array.  "device" is reserved for the device
+    twins of the warp and of the eroded paste, which are not built yet, and raises."""
+    from . import postprocess as PP
+    dev = next(model.parameters()).device
+    if _glue(glue) == "host":
+        img = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+        return PP.unblur_faces(img, landmarks, model, device=dev)
+    raise NotImplementedError("unblur_faces: the device twins of the warp and of the eroded paste are not built yet; use glue='host'")
+
+
 def film_schedule(inter_frames: int):
     """The order in which the reference fills the `inter_frames` frames between two given ones, as a list of model calls
     (left slot, right slot, target slot, dt).  Slot k of 0 .. inter_frames + 1 sits at time k / (inter_frames + 1) on an fp32 time axis;

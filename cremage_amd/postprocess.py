@@ -30,6 +30,13 @@ that a Cremage user finds the whole second-pass chain:
                                    (`spot_inpaint`), both ending in the blurred-mask blend (`blend_blurred_mask`; on the device
                                    cremage_amd.ops.blur_blend_u8, the same bytes).
 
+  face unblur / colorize           modules/unblur_face/face_unblur.py:129-162, :227-271: five landmarks -> similarity transform onto the
+                                   256 x 256 template -> warp -> network -> warp back -> paste under a 5 x 5 eroded mask
+                                   (`similarity_from_landmarks`, `warp_affine_u8`, `paste_warped_face`, `unblur_faces` /
+                                   `colorize_faces`).  Stated APPROXIMATIONS of cv.estimateAffinePartial2D (closed-form least squares,
+                                   no RANSAC), cv.warpAffine (its fixed-point scheme defined here in integers) and cv.erode, unpinned
+                                   against cv2 like the two above.  Host only: their device twins are not built.
+
 Pure Python + PIL + numpy; nothing above the "device twins" section touches the HIP library.
 
 Device twins (`resample_u8_host` and the `*_device` functions): the same arithmetic with the image staying on the GPU.  PIL resizes
@@ -684,6 +691,151 @@ def spot_inpaint_device(image: torch.Tensor, mask_gray_u8: np.ndarray, inpaint_f
     ph, pw = min(int(patch.shape[0]), H - y), min(int(patch.shape[1]), W - x)
     work[y:y + ph, x:x + pw] = patch[:ph, :pw, :3]  # not resized to the window: see spot_inpaint's QUIRK
     return work
+
+
+# ---------------------------------------------------------------------------------------------- face unblur / colorize
+# The glue around UnblurCremageModelV6 (modules/unblur_face/face_unblur.py:129-162 align_face, :227-271 process_face_image): five
+# landmarks -> similarity transform onto the 256 x 256 template -> warp -> network -> warp back -> paste under an eroded mask.
+# Detection (YuNet through cv2) stays outside: callers pass the landmarks, as they pass boxes to face fix.  cv2 does not exist in this
+# image, so what follows are stated APPROXIMATIONS of cv.estimateAffinePartial2D (a RANSAC over the five points with a Levenberg-
+# Marquardt refinement: here the closed-form least-squares fit over all five), cv.warpAffine (bilinear in cv2's fixed-point scheme;
+# its tables cannot be pinned, so the scheme is DEFINED below entirely in integers) and cv.erode - unpinned against cv2 like
+# `poisson_clone_host` and `mask_boxes`.
+UNBLUR_SIZE = 256
+_UNBLUR_PAD, _UNBLUR_SRC = 30, 112 + 2 * 30  # face_unblur.py:26-30: the 96 x 112 alignment template, centred in 112 and padded by 30
+#: the template's five landmarks (left eye, right eye, nose tip, left / right lip corner) in the 256 x 256 face, face_unblur.py:32-37
+UNBLUR_LANDMARKS_256 = tuple(((8 + _UNBLUR_PAD + x) * UNBLUR_SIZE / _UNBLUR_SRC, (_UNBLUR_PAD + y) * UNBLUR_SIZE / _UNBLUR_SRC)
+                             for x, y in ((30.2946, 51.6963), (65.5318, 51.5014), (48.0252, 71.7366), (33.5493, 92.3655), (62.7299, 92.2041)))
+WARP_POS_BITS = 5      # source positions in 1 / 32 pixel
+WARP_COEF_BITS = 10    # the matrix in 1 / 1024 pixel before the positions are cut to 1 / 32
+WARP_WEIGHT_BITS = 15  # the four bilinear weights (32 - fx | fx) * (32 - fy | fy) * 32 are integers that sum to 32768
+
+
+def similarity_from_landmarks(landmarks, template=UNBLUR_LANDMARKS_256) -> np.ndarray:
+    """The 2 x 3 float64 matrix [[a, -b, tx], [b, a, ty]] (rotation, uniform scale, shift: 4 degrees of freedom) that maps the five
+    landmarks onto the template in the least-squares sense, in closed form.  The landmarks are truncated to integers first, as
+    align_face does (face_unblur.py:145, astype(np.int32))."""
+    p = np.asarray(landmarks, dtype=np.float64).reshape(-1, 2).astype(np.int32).astype(np.float64)
+    q = np.asarray(template, dtype=np.float64).reshape(-1, 2)
+    if p.shape != q.shape or p.shape[0] < 2:
+        raise ValueError(f"similarity_from_landmarks: {p.shape[0]} landmarks for a template of {q.shape[0]}")
+    pm, qm = p.mean(axis=0), q.mean(axis=0)
+    pc, qc = p - pm, q - qm
+    den = float((pc * pc).sum())
+    if den <= 0.0:
+        raise ValueError("similarity_from_landmarks: the landmarks coincide")
+    a = float((pc[:, 0] * qc[:, 0] + pc[:, 1] * qc[:, 1]).sum()) / den
+    b = float((pc[:, 0] * qc[:, 1] - pc[:, 1] * qc[:, 0]).sum()) / den
+    return np.array([[a, -b, qm[0] - (a * pm[0] - b * pm[1])], [b, a, qm[1] - (b * pm[0] + a * pm[1])]], dtype=np.float64)
+
+
+def invert_affine(m) -> np.ndarray:
+    """cv.invertAffineTransform: the inverse of a 2 x 3 affine map, float64"""
+    m = np.asarray(m, dtype=np.float64).reshape(2, 3)
+    d = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    if d == 0.0:
+        raise ValueError("invert_affine: singular matrix")
+    i00, i01, i10, i11 = m[1, 1] / d, -m[0, 1] / d, -m[1, 0] / d, m[0, 0] / d
+    return np.array([[i00, i01, -(i00 * m[0, 2] + i01 * m[1, 2])], [i10, i11, -(i10 * m[0, 2] + i11 * m[1, 2])]], dtype=np.float64)
+
+
+def warp_affine_tables(dst_to_src, width: int, height: int):
+    """The integer tables that DEFINE `warp_affine_u8`: per destination column x  ax[x] = rint(m00 x 1024), bx[x] = rint(m10 x 1024); per
+    destination row y  x0[y] = rint((m01 y + m02) 1024) + 16, y0[y] = rint((m11 y + m12) 1024) + 16 (16: half of 1 / 32 pixel), all
+    int64 from float64 products, rint half to even.  The source position of (x, y) in 1 / 32 pixel is ((x0[y] + ax[x]) >> 5,
+    (y0[y] + bx[x]) >> 5), arithmetic shifts.  Positions are clipped to +- 2^40 so that no table entry overflows."""
+    m = np.asarray(dst_to_src, dtype=np.float64).reshape(2, 3)
+    scale = float(1 << WARP_COEF_BITS)
+    xs, ys = np.arange(width, dtype=np.float64), np.arange(height, dtype=np.float64)
+    lim = float(1 << 40)
+    cut = lambda v: np.clip(np.rint(v), -lim, lim).astype(np.int64)  # noqa: E731
+    half = 1 << (WARP_COEF_BITS - WARP_POS_BITS - 1)
+    return cut(m[0, 0] * xs * scale), cut(m[1, 0] * xs * scale), cut((m[0, 1] * ys + m[0, 2]) * scale) + half, cut((m[1, 1] * ys + m[1, 2]) * scale) + half
+
+
+def warp_affine_u8(src_u8_hwc: np.ndarray, dst_to_src, width: int, height: int) -> np.ndarray:
+    """Bilinear affine warp of a uint8 [h, w, C] image with a zero border, defined entirely in integers: destination pixel (x, y) reads the
+    source at the 1 / 32-pixel position of `warp_affine_tables`, its four neighbours weighted by (32 - fx | fx) (32 - fy | fy) 32 - integers
+    that sum to 2^15 - a neighbour outside the source counting as 0, and the sum is rounded by (s + 2^14) >> 15.  `dst_to_src` maps
+    destination to source coordinates: cv.warpAffine(src, M, size) is warp_affine_u8(src, invert_affine(M), *size)."""
+    src = np.ascontiguousarray(np.asarray(src_u8_hwc))
+    if src.ndim != 3 or src.dtype != np.uint8:
+        raise ValueError(f"warp_affine_u8: uint8 [h, w, C] image expected, got {src.dtype} {src.shape}")
+    h, w, _ = src.shape
+    ax, bx, x0, y0 = warp_affine_tables(dst_to_src, width, height)
+    shift = WARP_COEF_BITS - WARP_POS_BITS
+    X = (x0[:, None] + ax[None, :]) >> shift
+    Y = (y0[:, None] + bx[None, :]) >> shift
+    sx, sy = X >> WARP_POS_BITS, Y >> WARP_POS_BITS
+    fx, fy = X & 31, Y & 31
+    acc = np.zeros((height, width, src.shape[2]), dtype=np.int64)
+    for dy, wy in ((0, 32 - fy), (1, fy)):
+        for dx, wx in ((0, 32 - fx), (1, fx)):
+            px, py = sx + dx, sy + dy
+            inside = (px >= 0) & (px < w) & (py >= 0) & (py < h)
+            tap = src[np.clip(py, 0, h - 1), np.clip(px, 0, w - 1)].astype(np.int64)
+            acc += np.where(inside, wx * wy * 32, 0)[:, :, None] * tap
+    return ((acc + (1 << (WARP_WEIGHT_BITS - 1))) >> WARP_WEIGHT_BITS).astype(np.uint8)
+
+
+def erode5_mask(mask: np.ndarray) -> np.ndarray:
+    """cv.erode(mask, ones((5, 5))) of a boolean [H, W, C] mask, per channel: a pixel stays set when every pixel of its 5 x 5
+    neighbourhood that lies INSIDE the image is set - pixels outside the image do not constrain (cv2's default border value)."""
+    m = np.asarray(mask, dtype=bool)
+    H, W = m.shape[:2]
+    out = m.copy()
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            if dy == 0 and dx == 0:
+                continue
+            ys, yd = slice(max(dy, 0), H + min(dy, 0)), slice(max(-dy, 0), H + min(-dy, 0))
+            xs, xd = slice(max(dx, 0), W + min(dx, 0)), slice(max(-dx, 0), W + min(-dx, 0))
+            out[yd, xd] &= m[ys, xs]
+    return out
+
+
+def paste_warped_face(image_u8_hwc: np.ndarray, face_u8_hwc: np.ndarray, face_from_image) -> np.ndarray:
+    """process_face_image's paste (face_unblur.py:250-268): the processed face warped back to the image's size (`face_from_image` is the
+    2 x 3 matrix that aligned it, i.e. the destination-to-source map of this warp; the reference inverts it twice), the per-channel mask
+    `warped > 0`, eroded 5 x 5, and where the eroded mask is set the warped value replaces the image's - the reference's and / or
+    composite.  Every other byte of the image is returned untouched."""
+    image = np.asarray(image_u8_hwc)
+    if image.ndim != 3 or image.dtype != np.uint8 or np.asarray(face_u8_hwc).shape[2] != image.shape[2]:
+        raise ValueError("paste_warped_face: uint8 [H, W, C] image and [h, w, C] face expected")
+    warped = warp_affine_u8(face_u8_hwc, face_from_image, image.shape[1], image.shape[0])
+    return np.where(erode5_mask(warped > 0), warped, image)
+
+
+def _face_to_unit(face_u8_hwc: np.ndarray, device) -> torch.Tensor:
+    return (torch.from_numpy(np.ascontiguousarray(face_u8_hwc)).float() / 255.0).permute(2, 0, 1).unsqueeze(0).to(device)
+
+
+def _unit_to_face(y: torch.Tensor) -> np.ndarray:
+    """clamp(0, 1), then ToPILImage's mul(255).byte(): truncation (face_unblur.py:114-115)"""
+    return torch.clamp(y[0].detach().float(), 0, 1).mul(255).to(torch.uint8).permute(1, 2, 0).cpu().numpy()
+
+
+def unblur_faces(image_u8_hwc: np.ndarray, landmarks, model: Callable[[torch.Tensor], torch.Tensor], device="cpu") -> np.ndarray:
+    """process_face_image for an image whose faces were detected elsewhere.  image: uint8 [H, W, 3]; landmarks: per face five (x, y) points
+    (left eye, right eye, nose tip, left / right lip corner; YuNet's columns 4 .. 13); model: [1, 3, 256, 256] in [0, 1] -> the same shape
+    (UnblurCremageModelV6 with the unblur weights).  Every face is aligned on the ORIGINAL image first (align_face runs before the loop), then
+    run through the model - / 255, model, clamp(0, 1), truncation to bytes - and pasted back in turn.  Returns a new image."""
+    image = np.ascontiguousarray(np.asarray(image_u8_hwc))
+    if image.ndim != 3 or image.dtype != np.uint8 or image.shape[2] != 3:
+        raise ValueError(f"unblur_faces: uint8 [H, W, 3] image expected, got {image.dtype} {image.shape}")
+    mats = [similarity_from_landmarks(lm) for lm in landmarks]
+    aligned = [warp_affine_u8(image, invert_affine(m), UNBLUR_SIZE, UNBLUR_SIZE) for m in mats]
+    out = image
+    for m, face in zip(mats, aligned):
+        with torch.no_grad():
+            out = paste_warped_face(out, _unit_to_face(model(_face_to_unit(face, device))), m)
+    return out
+
+
+def colorize_faces(image_u8_hwc: np.ndarray, landmarks, model: Callable[[torch.Tensor], torch.Tensor], device="cpu") -> np.ndarray:
+    """`unblur_faces` with the colorize weights in `model`: the reference runs the same class and the same glue for both buttons
+    (face_unblur.py:201-224)."""
+    return unblur_faces(image_u8_hwc, landmarks, model, device)
 
 
 # ---------------------------------------------------------------------------------------------- PNG + generation_data

@@ -306,7 +306,8 @@ enum crg_route_kernel {
   CRG_ROUTE_CONV_PP = 3,    /* conv3_pp_kernel (conv_pp.hip): the staggered 256-pixel-tile 3x3 conv                                    */
   CRG_ROUTE_GEMM_RING = 4,  /* gemm_ring_kernel (gemm_ring.hip): persistent 256-row tiles                                              */
   CRG_ROUTE_GEMM_REG = 5,   /* gemm_kernel: register-staged operands (fp32 A, or fp32-class on unsplit operands)                       */
-  CRG_ROUTE_PLANES = 6      /* fp32-class / MX on pre-split planes (gemm_glds_kernel<.., NS = 2> or conv3_rowhalo_kernel, see rowhalo)      */
+  CRG_ROUTE_PLANES = 6,     /* fp32-class / MX on pre-split planes (gemm_glds_kernel<.., NS = 2> or conv3_rowhalo_kernel, see rowhalo)      */
+  CRG_ROUTE_CONVT = 7       /* conv_transpose_kernel (unblur.hip): four parity GEMMs on the source grid; wnt = tile width / 32, config = tile height / 32 */
 };
 enum crg_route_reduce {
   CRG_REDUCE_NONE = 0,
@@ -345,8 +346,14 @@ int crg_last_route(crg_ctx* ctx, crg_route* out);
  *                                                             source pixel (i + a - 1 + u, j + b - 1 + v) for output (2i + a, 2j + b):
  *                                                             kh in {0},{1,2} (a = 0) or {0,1},{2} (a = 1) for u = 0, 1; kw likewise.
  *                                                             Summed in fp32, then rounded (or split) once.  16 * Cout * Cin elements.
+ *   CRG_PACK_CONVT_UP2 [Cin][Cout][4][4] -> [4][Cout][4*Cin]  the parity image of ConvTranspose2d(kernel 4, stride 2, padding 1)
+ *                                                             (crg_conv_transpose2d; n_out = Cout, n_in = Cin, ksize = 4): slab (a, b)
+ *                                                             holds tap W[ci][co][3 - a - 2u][3 - b - 2v], the one that reads source pixel
+ *                                                             (i + a - 1 + u, j + b - 1 + v) for output (2i + a, 2j + b) - taps are
+ *                                                             SELECTED, each of the 16 lands in exactly one slab, nothing is summed.
+ *                                                             K order [Cin/64][u][v][64] when Cin % 64 == 0, else [u][v][Cin].
  * dst_hi (and dst_lo when non-NULL: the bf16 residual src - hi) are bf16, caller-allocated. */
-enum crg_pack_kind { CRG_PACK_LINEAR = 0, CRG_PACK_CONV = 1, CRG_PACK_GEGLU = 2, CRG_PACK_CONV_UP2 = 3 };
+enum crg_pack_kind { CRG_PACK_LINEAR = 0, CRG_PACK_CONV = 1, CRG_PACK_GEGLU = 2, CRG_PACK_CONV_UP2 = 3, CRG_PACK_CONVT_UP2 = 4 };
 int crg_pack_weight(crg_ctx* ctx, void* stream, const void* src, int src_dtype, int kind, int n_out, int n_in,
                     int ksize, void* dst_hi, void* dst_lo);
 /* bias for GEGLU packed the same way (fp32 in, fp32 out) */
@@ -823,6 +830,29 @@ typedef struct {
   float slope;
 } crg_film_act_args;
 int crg_film_act(crg_ctx* ctx, void* stream, const crg_film_act_args* args);
+
+/* ---- the face unblur / colorize network (unblur.hip; modules/unblur_face/cremage_model_v6.py) ------------------------------------------
+ * crg_conv_transpose2d: nn.ConvTranspose2d(Cin, Cout, kernel 4, stride 2, padding 1) in the fp32 class, one launch for all four output
+ *   parities:  y[n][2i+a][2j+b] = bias + sum_{u,v in {0,1}} W[:, :, 3-a-2u, 3-b-2v]^T x[n][i+a-1+u][j+b-1+v], x outside the image = 0 by
+ *   selection (never addressed), then SiLU when `silu` (ConvTransposeAct, cremage_model_v6.py:395-396).  x_hi, x_lo: the half-type planes
+ *   [N*H*W][Cin] of crg_split_bf16 / crg_groupnorm_add_act; w_hi, w_lo: crg_pack_weight(CRG_PACK_CONVT_UP2, split); bias fp32 [Cout] or
+ *   NULL; y fp32 [N][2H][2W][Cout] channels-last, dense, not overlapping the planes.  No zero-stuffed image and no zero tap exists; on a
+ *   grid of one row (column) the taps no pixel reaches are not read.  Three matrix passes lo*hi + hi*lo + hi*hi per k-step into one fp32
+ *   accumulator, whole K in one block, fixed order.  Cin % 8 == 0, Cout % 4 == 0, any H, W >= 1; pointers 16-byte aligned.  Sets the
+ *   route record (CRG_ROUTE_CONVT).  Profile slot: CRG_K_CONV_X3.
+ *
+ * crg_groupnorm_add_act: y = silu?(GroupNorm(x) * gamma + beta + skip) - the tail `x = gn2(x); x = x + skip; x = act2(x)` of the
+ *   post-norm residual blocks (cremage_model_v6.py:94-98, :194-198), and with skip = NULL the `gn1` + `act1` in front of conv2.  x fp32
+ *   [N][HW][C] dense; skip fp32 or NULL, rows ld_skip elements apart; y fp32 (or NULL) rows ld_y apart; y_hi / y_lo (both or none) the
+ *   half-type planes hi = half(y), lo = half(y - hi), rows ld_planes apart - a destination may be a column slice of a wider buffer, the
+ *   other columns are not touched.  gn_stats: the side channel [2][N*HW/32][C] of the conv that produced x (crg_conv_args.gn_stats), or
+ *   NULL: the statistics are then summed from x.  Either way they are folded in fp64.  workspace: N * groups * 64 * 16 bytes at most.
+ *   C % 8 == 0, groups <= 64 dividing C (any group size), HW >= 1.  Two launches.  Profile slots: CRG_K_GN_STATS, CRG_K_GN_APPLY. */
+int crg_conv_transpose2d(crg_ctx* ctx, void* stream, const void* x_hi, const void* x_lo, const void* w_hi, const void* w_lo, const float* bias, void* y,
+                         int N, int H, int W, int Cin, int Cout, int silu);
+int crg_groupnorm_add_act(crg_ctx* ctx, void* stream, const void* x, const void* skip, int64_t ld_skip, const float* gamma, const float* beta,
+                          const float* gn_stats, void* y, int64_t ld_y, void* y_hi, void* y_lo, int64_t ld_planes, void* workspace,
+                          int64_t workspace_bytes, int N, int HW, int C, int groups, float eps, int silu);
 
 #ifdef __cplusplus
 }
