@@ -337,6 +337,10 @@ SIGNATURES = {
     "crg_conv_transpose2d": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "crg_groupnorm_add_act": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                       c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_int]),
+    "crg_warp_affine_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, C.POINTER(C.c_double), c_int, c_void_p, c_int,
+                                   c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
+    "crg_paste_warped_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_int64,
+                                    c_int, c_int, C.POINTER(C.c_double), c_int, c_int, c_int, c_int]),
 }
 
 

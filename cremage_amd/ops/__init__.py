@@ -24,7 +24,8 @@ from .conv import affine_cast, conv1x1, conv2d, mx_conv_ok, split_bf16, upsample
 from .film import avg_pool2, flow_up2_add, leaky_split, scale_into, warp_flow
 from .frames import MAX_FRAMES, add_frames, attention_frames, blend_frames, conv_frames, conv_frames_thin, conv_frames_x3, frames_weight, lincomb_frames
 from .gemm import _gemm, last_route, linear, linear_transposed, linear_transposed_ok, ln_linear, ln_linear_auto, ln_linear_ok, rows_per_sample  # noqa: F401
-from .imaging import BLEND_GRAY, RESAMPLE_BITS, bilinear_tables, blur_blend_u8, lanczos_tables, poisson_clone, poisson_tables, resample_u8, upscale_noise, upscaled_size
+from .imaging import (BLEND_GRAY, RESAMPLE_BITS, bilinear_tables, blur_blend_u8, lanczos_tables, paste_warped_u8, poisson_clone, poisson_tables, resample_u8,
+                      upscale_noise, upscaled_size, warp_affine_u8)
 from .mx8 import dequant_mx8_host, ff_mx8_ok, linear_mx8, linear_mx8_host, packed_weight_mx8, quant_mx8, quant_mx8_host
 from .norms import group_norm, layer_norm, softmax_rows_
 from .packing import MX_X_LOG2, packed_geglu_bias, packed_ln_weight, packed_weight, packed_weight_mx, split_mx
@@ -41,7 +42,7 @@ __all__ = [
     "flow_up2_add", "frames_weight", "group_norm", "group_norm_add_act", "image_of", "image_of_stats", "lanczos_tables", "last_route", "layer_norm", "leaky_split",
     "lincomb_frames", "linear", "linear_mx8", "linear_mx8_host", "linear_transposed", "linear_transposed_ok", "ln_epi_ok", "ln_epi_wanted", "ln_linear",
     "ln_linear_auto", "ln_linear_ok", "mark_cfg_dup", "mx_conv_ok", "nchw_to_nhwc", "nhwc_to_nchw", "packed_geglu_bias", "packed_ln_weight",
-    "packed_weight", "packed_weight_mx", "packed_weight_mx8", "poisson_clone", "poisson_tables", "profile", "quant_mx8", "quant_mx8_host",
+    "packed_weight", "packed_weight_mx", "packed_weight_mx8", "paste_warped_u8", "poisson_clone", "poisson_tables", "profile", "quant_mx8", "quant_mx8_host",
     "resample_u8", "row_stats_parts", "rows_per_sample", "scale_into", "silu", "softmax_rows_", "split_bf16", "split_mx", "time_rows_of",
-    "timestep_embedding", "to_channels_last", "tokens_of", "upsample_subpixel_ok", "upscale_noise", "upscaled_size", "warp_flow",
+    "timestep_embedding", "to_channels_last", "tokens_of", "upsample_subpixel_ok", "upscale_noise", "upscaled_size", "warp_affine_u8", "warp_flow",
 ]

@@ -1,4 +1,5 @@
-"""Pixel- and latent-space image ops: the hires-fix latent upscale, PIL's Lanczos resize, the Poisson paste and the blurred-mask blend."""
+"""Pixel- and latent-space image ops: the hires-fix latent upscale, PIL's Lanczos resize, the Poisson paste, the blurred-mask blend,
+the affine warp and the eroded paste of face unblur / colorize."""
 import ctypes as C
 import functools
 import math
@@ -312,3 +313,111 @@ def blur_blend_u8(original: torch.Tensor, updated: torch.Tensor, mask: torch.Ten
     a.taps[:] = [float(v) for v in gaussian_taps_11()]
     _call("crg_blur_blend_u8", original, C.byref(a))
     return _written(out)
+
+
+# ---------------------------------------------------------------------------------- affine warp and eroded paste (face unblur / colorize)
+def _maps(dst_to_src, what: str):
+    """[2, 3] or [N, 2, 3] float64 maps (array-like or CPU tensor) -> (numpy [N, 6] float64 contiguous, batched)"""
+    import numpy as np
+    if torch.is_tensor(dst_to_src):
+        if dst_to_src.is_cuda:
+            raise L.CrgError(f"{what}: the maps are host data (array-like or a CPU tensor): they travel as kernel arguments")
+        dst_to_src = dst_to_src.detach().numpy()
+    m = np.ascontiguousarray(np.asarray(dst_to_src, dtype=np.float64))
+    if m.shape == (2, 3):
+        return m.reshape(1, 6), False
+    if m.ndim != 3 or tuple(m.shape[1:]) != (2, 3) or m.shape[0] < 1:
+        raise L.CrgError(f"{what}: [2, 3] or [N, 2, 3] maps expected, got {m.shape}")
+    return m.reshape(-1, 6), True
+
+
+def _u8_image(t: torch.Tensor, what: str):
+    """strided uint8 [H, W, C] with adjacent channels -> (H, W, C, row stride, pixel stride)"""
+    if t.dim() != 3 or t.dtype != torch.uint8:
+        raise L.CrgError(f"{what}: uint8 [H, W, C] image expected, got {tuple(t.shape)} {t.dtype}")
+    H, W, ch = t.shape
+    if ch < 1 or ch > 4 or H < 1 or W < 1:
+        raise L.CrgError(f"{what}: a {H}x{W}x{ch} image: 1..4 channels and at least one pixel are needed")
+    if ch > 1 and t.stride(2) != 1:
+        raise L.CrgError(f"{what}: the channels of a pixel must be adjacent")
+    if t.stride(0) < 0 or t.stride(1) < 0:
+        raise L.CrgError(f"{what}: strides must not be negative")
+    return H, W, ch, t.stride(0), t.stride(1)
+
+
+def _dbl(m):
+    return m.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def warp_affine_u8(src: torch.Tensor, dst_to_src, size: Tuple[int, int], *, out: Optional[torch.Tensor] = None,
+                   out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+    """postprocess.warp_affine_u8 on the device, equal to its bytes (crg_warp_affine_u8): N destination images of one source in one call.
+    src: uint8 [h, w, C], C in 1..4, channels adjacent - a view is fine (a window of a larger image, the RGB of an RGBA buffer).
+    dst_to_src: [2, 3] or [N, 2, 3] float64 destination-to-source maps, array-like or a CPU tensor: they are read now and travel as kernel
+    arguments, nothing is uploaded.  size = (W, H) of a destination, as warp_affine_u8(..., width, height).  out_dtype uint8: the result is
+    [H, W, C] ([N, H, W, C] for [N, 2, 3] maps); float32: [N, C, H, W] holding byte / 255.0 - torch.from_numpy(host).float() / 255.0 in the
+    network's input layout, bit for bit.  `out`: a tensor of the result's shape and dtype, any strides with adjacent channels for uint8 (a
+    window), no overlap with src; default a new contiguous tensor.  Returns the result."""
+    _need_cuda(src, out)
+    h, w, ch, ssy, ssx = _u8_image(src, "warp_affine_u8: src")
+    m, batched = _maps(dst_to_src, "warp_affine_u8")
+    n = m.shape[0]
+    W, H = int(size[0]), int(size[1])
+    if W < 1 or H < 1:
+        raise L.CrgError(f"warp_affine_u8: empty size {(W, H)}")
+    dt = out.dtype if out is not None else out_dtype
+    if dt not in (torch.uint8, torch.float32):
+        raise L.CrgError(f"warp_affine_u8: out_dtype must be uint8 or float32, got {dt}")
+    f32 = dt == torch.float32
+    shape = (n, ch, H, W) if f32 else ((n, H, W, ch) if batched else (H, W, ch))
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=src.device)
+    elif tuple(out.shape) != shape or out.device != src.device:
+        raise L.CrgError(f"warp_affine_u8: {dt} out of shape {shape} on {src.device} expected, got {tuple(out.shape)} on {out.device}")
+    if any(s < 0 for s in out.stride()):
+        raise L.CrgError("warp_affine_u8: strides must not be negative")
+    if f32:
+        sn, sc, sy, sx = out.stride()
+    else:
+        if ch > 1 and out.stride(-1) != 1:
+            raise L.CrgError("warp_affine_u8: the channels of a pixel must be adjacent")
+        sn, sc, sy, sx = (out.stride(0) if batched else 0), 1, out.stride(-3), out.stride(-2)
+    _call("crg_warp_affine_u8", src, _p(src), ssy, ssx, h, w, ch, _dbl(m), n, _p(out), int(f32), sn, sc, sy, sx, H, W)
+    return _written(out)
+
+
+def paste_warped_u8(image: torch.Tensor, face: torch.Tensor, face_from_image, *, rect: Optional[Tuple[int, int, int, int]] = None) -> torch.Tensor:
+    """postprocess.paste_warped_face on the device, IN PLACE on `image`, one launch (crg_paste_warped_u8), equal to its bytes: the face
+    warped to the image's size with the destination-to-source map `face_from_image` ([2, 3] float64, host data), the per-channel mask
+    warped > 0 eroded 5 x 5, the warped byte stored where the eroded mask is set; no other byte of the image is written.
+    image: uint8 [H, W, C], C in 1..4, channels adjacent (a view is fine).  face: uint8 [h, w, C], or fp32 [C, h, w] / [1, C, h, w] with
+    any strides - the network's output as it is - read as clamp(0, 1).mul(255).byte() (postprocess._unit_to_face).
+    rect = (x, y, w, h): the caller's statement that the warped face is 0 outside it; only tiles that touch it are launched.  None:
+    postprocess.warped_footprint.  Returns `image`."""
+    _need_cuda(image, face)
+    H, W, ch, isy, isx = _u8_image(image, "paste_warped_u8: image")
+    m, batched = _maps(face_from_image, "paste_warped_u8")
+    if batched:
+        raise L.CrgError("paste_warped_u8: one [2, 3] map expected")
+    if face.device != image.device:
+        raise L.CrgError(f"paste_warped_u8: image on {image.device}, face on {face.device}")
+    if face.dtype == torch.uint8:
+        h, w, fch, fsy, fsx = _u8_image(face, "paste_warped_u8: face")
+        f32, fsc = 0, 1
+    elif face.dtype == torch.float32 and (face.dim() == 3 or (face.dim() == 4 and face.shape[0] == 1)):
+        f = face[0] if face.dim() == 4 else face
+        fch, h, w = f.shape
+        fsc, fsy, fsx = f.stride()
+        f32 = 1
+        if min(fsc, fsy, fsx) < 0 or h < 1 or w < 1:
+            raise L.CrgError("paste_warped_u8: an empty face or a negative stride")
+    else:
+        raise L.CrgError(f"paste_warped_u8: uint8 [h, w, C] or float32 [C, h, w] / [1, C, h, w] face expected, got {tuple(face.shape)} {face.dtype}")
+    if fch != ch:
+        raise L.CrgError(f"paste_warped_u8: a face of {fch} channels for an image of {ch}")
+    if rect is None:
+        from ..postprocess import warped_footprint
+        rect = warped_footprint(m.reshape(2, 3), (w, h), (W, H))
+    rx, ry, rw, rh = (int(v) for v in rect)
+    _call("crg_paste_warped_u8", image, _p(image), isy, isx, H, W, ch, _p(face), f32, fsc, fsy, fsx, h, w, _dbl(m), rx, ry, rw, rh)
+    return _written(image)

@@ -459,19 +459,46 @@ def build_synthetic_unblur(device="cuda", seed: int = 1234, fill: bool = True):
     return m.eval()
 
 
+def _graphed_unblur(model):
+    """The model call as a hipGraph replay: one GraphedModule per model object, kept on it and reused across calls (one capture for the
+    [1, 3, 256, 256] face; warm-up, the weight stamp and `strict` are GraphedModule's)."""
+    g = getattr(model, "_crg_graphed", None)
+    if g is None or g.module is not model:
+        from .graphs import GraphedModule
+        g = GraphedModule(model, const_args=())
+        object.__setattr__(model, "_crg_graphed", g)  # a plain attribute: not a submodule, not in the state dict
+    return g
+
+
 @torch.no_grad()
-def unblur_faces(model, image, landmarks, *, glue: str = "host"):
+def unblur_faces(model, image, landmarks, *, glue: str = "host", graph: bool = False):
     """The Face Fixer's "Unblur face" / "Colorize face" on an image whose faces were detected elsewhere (face_unblur.py:227-271): per face
     the five landmarks give the similarity transform onto the 256 x 256 template, the aligned face goes through `model` (the unblur or
     the colorize weights) and is warped back and pasted under its eroded mask.  image: uint8 [H, W, 3] (numpy array or tensor); landmarks:
-    [faces, 5, 2].  glue "host": numpy on the host (postprocess.unblur_faces), returns a numpy array.  "device" is reserved for the device
-    twins of the warp and of the eroded paste, which are not built yet, and raises."""
+    [faces, 5, 2].  glue "host": numpy on the host (postprocess.unblur_faces), returns a numpy array.  glue "device": the image is uploaded
+    once (a tensor on the device is taken as it is and not modified), the warp and the eroded paste run as kernels
+    (postprocess.unblur_faces_device: the host arm's bytes, no download and no stream synchronisation per face) and the result is a uint8
+    [H, W, 3] tensor on the model's device; a model on the CPU is a CrgError.  graph=True, in either arm: the model call is a hipGraph
+    replay (`cremage_amd.graphs.GraphedModule`, kept on the model object) - the same kernels in the same order, the same bits."""
     from . import postprocess as PP
+    from ._lib import CrgError
     dev = next(model.parameters()).device
-    if _glue(glue) == "host":
+    glue = _glue(glue)
+    if dev.type != "cuda" and (glue == "device" or graph):
+        raise CrgError(f"unblur_faces: glue='device' and graph=True need the model on a HIP device, it is on {dev}")
+    call = _graphed_unblur(model) if graph else model
+    if glue == "host":
         img = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
-        return PP.unblur_faces(img, landmarks, model, device=dev)
-    raise NotImplementedError("unblur_faces: the device twins of the warp and of the eroded paste are not built yet; use glue='host'")
+        return PP.unblur_faces(img, landmarks, call, device=dev)
+    img = image.detach().to(dev) if torch.is_tensor(image) else torch.from_numpy(np.ascontiguousarray(np.asarray(image))).to(dev)
+    with torch.cuda.device(dev):
+        return PP.unblur_faces_device(img, landmarks, call)
+
+
+def colorize_faces(model, image, landmarks, *, glue: str = "host", graph: bool = False):
+    """`unblur_faces` with the colorize weights in `model`: the reference runs the same class and the same glue for both buttons
+    (face_unblur.py:201-224)."""
+    return unblur_faces(model, image, landmarks, glue=glue, graph=graph)
 
 
 def film_schedule(inter_frames: int):

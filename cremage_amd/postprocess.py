@@ -806,6 +806,43 @@ def paste_warped_face(image_u8_hwc: np.ndarray, face_u8_hwc: np.ndarray, face_fr
     return np.where(erode5_mask(warped > 0), warped, image)
 
 
+def warped_footprint(face_from_image, face_size: Tuple[int, int], image_size: Tuple[int, int]) -> Tuple[int, int, int, int]:
+    """A rectangle (x, y, w, h) of the image outside which `warp_affine_u8(face, face_from_image, W, H)` is 0 whatever the face holds:
+    what `ops.paste_warped_u8` launches its tiles over.  face_size = (w, h), image_size = (W, H).  Conservative, never tight by promise.
+    A destination pixel has a non-zero weight on a source pixel only when its computed position lies in [-1, w] x [-1, h].  The computed
+    position is the real one, m p + t, moved by less than 1 / 16 pixel per axis: each of the two table entries lies within 2^-11 pixel of
+    its real value, the offset adds 1 / 64 and the cut to 1 / 32 pixel takes away less than 1 / 32.  So the pixel's REAL position lies in
+    the support grown by 1 / 16 - here by 1 / 8, the other half paying for the rounding of this function's own float64 arithmetic - and
+    the pixel lies in the image of that rectangle under the inverse map, a parallelogram whose bounding box is that of its four corners.
+    The whole image is returned where that reasoning does not hold: a singular map, a non-finite intermediate, or coefficients large
+    enough for a table entry to reach the +- 2^40 clip (the clipped position is then not near the real one).  (0, 0, 0, 0): the face
+    does not reach the image."""
+    m = np.asarray(face_from_image, dtype=np.float64).reshape(2, 3)
+    (w, h), (W, H) = (int(v) for v in face_size), (int(v) for v in image_size)
+    whole = (0, 0, W, H)
+    if not np.all(np.isfinite(m)):
+        return whole
+    scale, lim = float(1 << WARP_COEF_BITS), float(1 << 40)
+    reach = max(abs(m[0, 0]) * W, abs(m[1, 0]) * W, abs(m[0, 1]) * H + abs(m[0, 2]), abs(m[1, 1]) * H + abs(m[1, 2]))
+    if not reach * scale < lim / 2:
+        return whole
+    d = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    with np.errstate(all="ignore"):
+        inv = np.array([[m[1, 1], -m[0, 1]], [-m[1, 0], m[0, 0]]]) / d
+        grow = 1.0 / 8.0
+        corners = np.array([[sx, sy] for sx in (-1.0 - grow, w + grow) for sy in (-1.0 - grow, h + grow)]) - m[:, 2]
+        dst = corners @ inv.T
+    if d == 0.0 or not np.all(np.isfinite(inv)) or not np.all(np.isfinite(dst)) or np.abs(dst).max() >= lim:
+        return whole
+    pad = 1e-6 * (1.0 + np.abs(dst).max())  # float64 rounding of the inverse and of the products above, with a wide margin
+    x0, y0 = (int(np.floor(v - pad)) for v in dst.min(axis=0))
+    x1, y1 = (int(np.ceil(v + pad)) for v in dst.max(axis=0))
+    x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W - 1), min(y1, H - 1)
+    if x1 < x0 or y1 < y0:
+        return (0, 0, 0, 0)
+    return (x0, y0, x1 - x0 + 1, y1 - y0 + 1)
+
+
 def _face_to_unit(face_u8_hwc: np.ndarray, device) -> torch.Tensor:
     return (torch.from_numpy(np.ascontiguousarray(face_u8_hwc)).float() / 255.0).permute(2, 0, 1).unsqueeze(0).to(device)
 
@@ -836,6 +873,33 @@ def colorize_faces(image_u8_hwc: np.ndarray, landmarks, model: Callable[[torch.T
     """`unblur_faces` with the colorize weights in `model`: the reference runs the same class and the same glue for both buttons
     (face_unblur.py:201-224)."""
     return unblur_faces(image_u8_hwc, landmarks, model, device)
+
+
+def unblur_faces_device(image_u8_dev: torch.Tensor, landmarks, model: Callable[[torch.Tensor], torch.Tensor]) -> torch.Tensor:
+    """`unblur_faces` with the image on the device from end to end, equal to its bytes: the matrices are fitted on the host (five points,
+    float64), ONE `ops.warp_affine_u8` call aligns every face on the ORIGINAL image straight into the network's fp32 input, then per face,
+    in the host loop's order, `model` on one face (batch 1, as on the host: the same kernels, hence the same bits) and
+    `ops.paste_warped_u8` of its output, read as it is, onto a working copy.  Nothing is downloaded and nothing waits for the stream.
+    image: uint8 [H, W, 3] on the device, not modified.  Returns a new uint8 [H, W, 3] tensor there."""
+    from . import ops
+    image = image_u8_dev
+    if not torch.is_tensor(image) or image.dim() != 3 or image.dtype != torch.uint8 or image.shape[2] != 3:
+        raise ValueError("unblur_faces_device: uint8 [H, W, 3] tensor expected")
+    mats = [similarity_from_landmarks(lm) for lm in landmarks]
+    work = image.clone(memory_format=torch.contiguous_format)
+    if not mats:
+        return work
+    x = ops.empty_image(len(mats), 3, UNBLUR_SIZE, UNBLUR_SIZE, torch.float32, image.device)  # channels-last: what the network reads
+    ops.warp_affine_u8(image, np.stack([invert_affine(m) for m in mats]), (UNBLUR_SIZE, UNBLUR_SIZE), out=x)
+    for i, m in enumerate(mats):
+        with torch.no_grad():
+            ops.paste_warped_u8(work, model(x[i:i + 1]), m)
+    return work
+
+
+def colorize_faces_device(image_u8_dev: torch.Tensor, landmarks, model: Callable[[torch.Tensor], torch.Tensor]) -> torch.Tensor:
+    """`unblur_faces_device` with the colorize weights in `model` (see `colorize_faces`)."""
+    return unblur_faces_device(image_u8_dev, landmarks, model)
 
 
 # ---------------------------------------------------------------------------------------------- PNG + generation_data

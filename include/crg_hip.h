@@ -854,6 +854,38 @@ int crg_groupnorm_add_act(crg_ctx* ctx, void* stream, const void* x, const void*
                           const float* gn_stats, void* y, int64_t ld_y, void* y_hi, void* y_lo, int64_t ld_planes, void* workspace,
                           int64_t workspace_bytes, int N, int HW, int C, int groups, float eps, int silu);
 
+/* ---- the glue of face unblur / colorize (warp_paste.hip; cremage_amd.postprocess.warp_affine_u8 / paste_warped_face are the definitions) ----
+ * Both warp a uint8 image with a 2 x 3 destination-to-source map m = (m00, m01, m02, m10, m11, m12), six float64 values per map behind a
+ * HOST pointer that is read when the call is made: the coefficients travel as kernel arguments, nothing is uploaded or cached.  Per
+ * destination pixel (x, y), in IEEE double, every operation rounded on its own (no fused multiply-add), cut(v) = (int64) clip(rint(v),
+ * -2^40, 2^40) with rint half to even:
+ *   ax = cut(m00 * x * 1024), bx = cut(m10 * x * 1024), x0 = cut((m01 * y + m02) * 1024) + 16, y0 = cut((m11 * y + m12) * 1024) + 16
+ *   X = (x0 + ax) >> 5, Y = (y0 + bx) >> 5            the source position in 1 / 32 pixel; 64-bit, arithmetic shifts (towards -inf)
+ *   sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31
+ *   s[c] = sum over the four neighbours (sx + dx, sy + dy) INSIDE the source of (dx ? fx : 32 - fx) * (dy ? fy : 32 - fy) * 32 * src[..][c]
+ *   warped[c] = (s[c] + 2^14) >> 15                    integers throughout; a neighbour outside the source counts 0 and is never read
+ * Images are strided, channels adjacent, C in 1..4: views are fine (a window of a larger image, the RGB of an RGBA buffer).
+ *
+ * crg_warp_affine_u8: N destination images of one source in one call (one launch per 16 maps).  src uint8 [h][w][C], strides in bytes;
+ *   dst_to_src 6 * N doubles; dst_f32 = 0: dst uint8 [N][H][W][C], strides in bytes, dst_sc = 1; dst_f32 = 1: dst fp32 [N][C][H][W],
+ *   strides in ELEMENTS, holding (float)warped / 255.0f with the division correctly rounded - torch's .float() / 255.0 of the bytes, in
+ *   the layout the network reads.  dst must not overlap src.
+ * crg_paste_warped_u8: paste_warped_face in one launch, IN PLACE on image uint8 [H][W][C] (strides in bytes).  face: uint8 [h][w][C]
+ *   (face_f32 = 0, face_sc = 1) or fp32 [C][h][w] (face_f32 = 1), strides in ELEMENTS of its type; an fp32 value v is read as the byte
+ *   (uint8)(fminf(fmaxf(v, 0), 1) * 255.0f) - one fp32 product, truncation: clamp(0, 1).mul(255).byte(); values are finite.  Per pixel
+ *   and channel: warped as above, mask = warped > 0, eroded 5 x 5 where neighbours outside the IMAGE do not constrain, and where the
+ *   eroded mask is set the warped byte is stored.  No other byte of the image is written, none is read; a pixel may take some channels
+ *   and keep others.  rect (x, y, w, h), inside the image: the caller's statement that warped is 0 outside it
+ *   (postprocess.warped_footprint); only the 64 x 16 tiles that touch it are launched, halo pixels are computed from the map whatever the
+ *   rectangle says, so a correct rectangle changes no byte.  An empty rectangle launches nothing.  The face must not overlap the image.
+ * Errors (-22, before any launch): C outside 1..4, an empty size, a pixel stride smaller than C, a negative stride, a coefficient that is
+ * not finite, overlap.  No atomics, no host synchronisation, no allocation, no scratch.  Profile slot: CRG_K_ELEMENTWISE. */
+int crg_warp_affine_u8(crg_ctx* ctx, void* stream, const void* src, int64_t src_sy, int64_t src_sx, int h, int w, int C, const double* dst_to_src,
+                       int N, void* dst, int dst_f32, int64_t dst_sn, int64_t dst_sc, int64_t dst_sy, int64_t dst_sx, int H, int W);
+int crg_paste_warped_u8(crg_ctx* ctx, void* stream, void* image, int64_t img_sy, int64_t img_sx, int H, int W, int C, const void* face,
+                        int face_f32, int64_t face_sc, int64_t face_sy, int64_t face_sx, int h, int w, const double* face_from_image, int rect_x,
+                        int rect_y, int rect_w, int rect_h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,9 +8,14 @@
   * one model call in three arms, in alternating triples inside one process (device events around each call, all warmed up): this path,
     the plain-torch restatement on PyTorch-ROCm fp32, and this path inside `composed_arm` - plus this path's device time per kernel family;
   * --parity: rel-L2 of the composed arm and of this path against every fixture of tests/golden/unblur_*.npz, per tensor - the figures
-    the bounds of tests/test_unblur_models_gpu.py are made of.
+    the bounds of tests/test_unblur_models_gpu.py are made of;
+  * --glue: pipeline.unblur_faces on one face of a 512 x 512 and of a 1024 x 1024 image, glue "host" against glue "device" in alternating
+    triples (host clock around a call that ends in a device synchronise; median), with the model call taken off and, as a direct
+    reading of the glue, with an identity model; the two glue kernels alone, replayed from a captured graph; and the eager model call
+    against its hipGraph replay (graph=True), alternating, with what the graph's memory pool holds.  These rows take the place of the
+    three-arm model rows.
 
-    python tools/unblur_time.py [--reps 20] [--triples 5] [--parity] [--skip-model] [--skip-kernels]
+    python tools/unblur_time.py [--reps 20] [--triples 5] [--parity] [--glue] [--skip-model] [--skip-kernels]
 Prints one JSON line per measurement.  Nothing is asserted."""
 import argparse
 import json
@@ -133,11 +138,89 @@ def parity_rows(m):
                 ref_own=meta["ref_fp32_vs_fp64"][k])
 
 
+def wall(fn):
+    """milliseconds of fn on the host clock, the device drained before and after"""
+    import time
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    y = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, y
+
+
+class _Identity(torch.nn.Module):
+    """a model that costs nothing: what is left of an arm is its glue"""
+
+    def __init__(self):
+        super().__init__()
+        self.one = torch.nn.Parameter(torch.ones(()))
+
+    def forward(self, x):
+        return x
+
+
+def glue_rows(triples, reps, m):
+    import numpy as np
+    from cremage_amd import pipeline, postprocess as PP
+    ident = _Identity().to(DEV)
+    tpl = np.array(PP.UNBLUR_LANDMARKS_256)
+    with torch.no_grad():
+        x = UC.full_input(1).to(DEV)
+        for _ in range(2):
+            m(x)
+        model_ms = statistics.median(wall(lambda: m(x))[0] for _ in range(max(triples, 3)))
+        for side in (512, 1024):
+            img = np.random.RandomState(side).randint(1, 256, size=(side, side, 3)).astype(np.uint8)
+            lms = [tpl * (side / 640.0) + [side * 0.3, side * 0.25]]  # a face of 0.4 of the image's side
+            mat = PP.similarity_from_landmarks(lms[0])
+            row = dict(what="glue", image=[side, side], faces=1, model_call_ms=model_ms, footprint=list(PP.warped_footprint(mat, (256, 256), (side, side))))
+            for name, model in (("", m), ("identity_", ident)):
+                host = lambda: pipeline.unblur_faces(model, img, lms, glue="host")  # noqa: E731
+                dev = lambda: pipeline.unblur_faces(model, img, lms, glue="device")  # noqa: E731
+                a, b = host(), dev()
+                row[name + "equal"] = bool(np.array_equal(a, b.cpu().numpy()))
+                th, td = [], []
+                for _ in range(triples):
+                    th.append(wall(host)[0])
+                    td.append(wall(dev)[0])
+                row.update({name + "host_ms": statistics.median(th), name + "host_ms_all": [round(t, 2) for t in th],
+                            name + "device_ms": statistics.median(td), name + "device_ms_all": [round(t, 2) for t in td]})
+            row["host_outside_model_ms"] = row["host_ms"] - model_ms
+            row["device_outside_model_ms"] = row["device_ms"] - model_ms
+            # the two kernels alone, replayed from a graph: the coefficients are kernel arguments, so they are captured
+            imgd = torch.from_numpy(img).to(DEV)
+            face = torch.rand(1, 3, 256, 256, device=DEV).contiguous(memory_format=torch.channels_last)
+            xin = ops.empty_image(1, 3, 256, 256, torch.float32, DEV)
+            inv = PP.invert_affine(mat)
+            rect = PP.warped_footprint(mat, (256, 256), (side, side))
+            w = graph_ms(lambda: ops.warp_affine_u8(imgd, inv[None], (256, 256), out=xin), reps)
+            p = graph_ms(lambda: ops.paste_warped_u8(imgd, face, mat, rect=rect), reps)
+            pw = graph_ms(lambda: ops.paste_warped_u8(imgd, face, mat, rect=(0, 0, side, side)), reps)
+            row.update(warp_kernel_ms=w[0], warp_kernel_ms_min=w[1], paste_kernel_ms=p[0], paste_kernel_ms_min=p[1], paste_whole_image_ms=pw[0])
+            out(**row)
+        # eager call against graph replay, alternating
+        torch.cuda.synchronize()
+        base, base_res = torch.cuda.memory_allocated(), torch.cuda.memory_reserved()
+        g = pipeline._graphed_unblur(m)
+        g(x)
+        torch.cuda.synchronize()
+        pool, pool_res = torch.cuda.memory_allocated() - base, torch.cuda.memory_reserved() - base_res
+        same = bool(torch.equal(g(x), m(x)))
+        te, tg = [], []
+        for _ in range(max(triples, 3)):
+            te.append(wall(lambda: m(x))[0])
+            tg.append(wall(lambda: g(x))[0])
+        out(what="model_call_graph", eager_ms=statistics.median(te), eager_ms_all=[round(t, 2) for t in te], replay_ms=statistics.median(tg),
+            replay_ms_all=[round(t, 2) for t in tg], equal=same, captures=g.captures, replays=g.replays, graph_held_gb=pool * 1e-9, graph_reserved_gb=pool_res * 1e-9,
+            peak_gb=torch.cuda.max_memory_allocated() * 1e-9)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--triples", type=int, default=5)
     ap.add_argument("--parity", action="store_true")
+    ap.add_argument("--glue", action="store_true")
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-kernels", action="store_true")
     a = ap.parse_args()
@@ -152,5 +235,7 @@ if __name__ == "__main__":
         model = build_synthetic_unblur(DEV, UC.SEED)
     if a.parity:
         parity_rows(model)
-    if model is not None:
+    if model is not None and a.glue:
+        glue_rows(a.triples, a.reps, model)
+    elif model is not None:
         model_rows(a.triples, model)
