@@ -341,6 +341,9 @@ SIGNATURES = {
                                    c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
     "crg_paste_warped_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int64, c_int64, c_int64,
                                     c_int, c_int, C.POINTER(C.c_double), c_int, c_int, c_int, c_int]),
+    "crg_relu_pool_proj": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
+    "crg_hed_fuse": (c_int, [c_void_p, c_void_p, c_int, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int, c_int, c_int]),
 }
 
 

@@ -17,7 +17,7 @@ LIB_F16 = os.path.join(HERE, "libcrg_hip_f16.so")  # the same sources with -DCRG
 # the long-compiling units first: the pool starts its jobs in this order
 SOURCES = ["gemm_glds_gemm.hip", "gemm_glds_conv.hip", "conv_rowhalo.hip", "video.hip", "video_x3.hip", "attention.hip", "conv_pp.hip", "small_ops.hip",
            "gemm_ring.hip", "lngemm.hip", "splitk_reduce.hip", "gemm_conv.hip", "crg_api.hip", "norms.hip", "poisson.hip", "blur_blend.hip", "mx8.hip",
-           "attention_x3.hip", "film.hip", "unblur.hip", "warp_paste.hip"]
+           "attention_x3.hip", "film.hip", "unblur.hip", "warp_paste.hip", "annot.hip"]
 # every header an object may depend on: a change to any of them rebuilds everything (found by listing, so that none can be missing)
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(HERE, "..", "include", "crg_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -26,8 +26,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # attention_x3.hip, video.hip, video_x3.hip: the compiler's resource report is read back and held against the kernel's budget (_check_budget).
 EXTRA_FLAGS = {"attention.hip": ["-fno-honor-nans"], "attention_x3.hip": ["-Rpass-analysis=kernel-resource-usage"],
                "video.hip": ["-Rpass-analysis=kernel-resource-usage"], "video_x3.hip": ["-Rpass-analysis=kernel-resource-usage"],
-               "unblur.hip": ["-Rpass-analysis=kernel-resource-usage"]}
-BUDGET_CHECKED = {"attention_x3.hip", "video.hip", "video_x3.hip", "unblur.hip"}  # no scratch, at most 512 registers per lane (VGPR + AGPR); the LDS bound is a static_assert
+               "unblur.hip": ["-Rpass-analysis=kernel-resource-usage"], "annot.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+BUDGET_CHECKED = {"attention_x3.hip", "video.hip", "video_x3.hip", "unblur.hip", "annot.hip"}  # no scratch, at most 512 registers per lane (VGPR + AGPR); the LDS bound is a static_assert
 
 
 def _hipcc():

@@ -19,6 +19,7 @@ from .. import knobs  # noqa: F401  (`ops.knobs` is the module itself; no knob i
 # (underscore names: the launch plumbing and the statistics side channel, for tests that call an entry point of the library directly)
 from ._base import (HALF, TensorKeyedCache, _h, _st, clear_weight_cache, empty_image, f32_vec, image_of, image_of_stats,  # noqa: F401
                     nchw_to_nhwc, nhwc_to_nchw, profile, to_channels_last, tokens_of)
+from .annot import HED_MAX_MAPS, hed_fuse, relu_pool_proj
 from .attn import attention, attention_rows_v, attention_x3_ok
 from .conv import affine_cast, conv1x1, conv2d, mx_conv_ok, split_bf16, upsample_subpixel_ok
 from .film import avg_pool2, flow_up2_add, leaky_split, scale_into, warp_flow
@@ -35,14 +36,14 @@ from .unblur import conv_transpose2d, group_norm_add_act
 from .steps import KSTEP_KINDS, STEP_KINDS, axpby_, cfg_ddim_step_, cfg_dpmpp2m_step_, cfg_euler_step_, cfg_kstep_, cfg_sampler_step_, silu, timestep_embedding
 
 __all__ = [
-    "BLEND_GRAY", "GN_STATS_MIN_HW", "HALF", "KSTEP_KINDS", "MAX_FRAMES", "MX_X_LOG2", "RESAMPLE_BITS", "STEP_KINDS", "TensorKeyedCache", "add_frames",
+    "BLEND_GRAY", "GN_STATS_MIN_HW", "HALF", "HED_MAX_MAPS", "KSTEP_KINDS", "MAX_FRAMES", "MX_X_LOG2", "RESAMPLE_BITS", "STEP_KINDS", "TensorKeyedCache", "add_frames",
     "affine_cast", "attach_time_rows", "attention", "attention_frames", "attention_rows_v", "attention_x3_ok", "avg_pool2", "axpby_", "bilinear_tables",
     "blend_frames", "blur_blend_u8", "cfg_ddim_step_", "cfg_dpmpp2m_step_", "cfg_euler_step_", "cfg_kstep_", "cfg_sampler_step_", "clear_weight_cache",
     "conv1x1", "conv2d", "conv_transpose2d", "conv_frames", "conv_frames_thin", "conv_frames_x3", "dequant_mx8_host", "dup_batch", "empty_image", "f32_vec", "ff_mx8_ok",
-    "flow_up2_add", "frames_weight", "group_norm", "group_norm_add_act", "image_of", "image_of_stats", "lanczos_tables", "last_route", "layer_norm", "leaky_split",
+    "flow_up2_add", "frames_weight", "group_norm", "group_norm_add_act", "hed_fuse", "image_of", "image_of_stats", "lanczos_tables", "last_route", "layer_norm", "leaky_split",
     "lincomb_frames", "linear", "linear_mx8", "linear_mx8_host", "linear_transposed", "linear_transposed_ok", "ln_epi_ok", "ln_epi_wanted", "ln_linear",
     "ln_linear_auto", "ln_linear_ok", "mark_cfg_dup", "mx_conv_ok", "nchw_to_nhwc", "nhwc_to_nchw", "packed_geglu_bias", "packed_ln_weight",
     "packed_weight", "packed_weight_mx", "packed_weight_mx8", "paste_warped_u8", "poisson_clone", "poisson_tables", "profile", "quant_mx8", "quant_mx8_host",
-    "resample_u8", "row_stats_parts", "rows_per_sample", "scale_into", "silu", "softmax_rows_", "split_bf16", "split_mx", "time_rows_of",
+    "relu_pool_proj", "resample_u8", "row_stats_parts", "rows_per_sample", "scale_into", "silu", "softmax_rows_", "split_bf16", "split_mx", "time_rows_of",
     "timestep_embedding", "to_channels_last", "tokens_of", "upsample_subpixel_ok", "upscale_noise", "upscaled_size", "warp_affine_u8", "warp_flow",
 ]

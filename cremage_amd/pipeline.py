@@ -501,6 +501,88 @@ def colorize_faces(model, image, landmarks, *, glue: str = "host", graph: bool =
     return unblur_faces(model, image, landmarks, glue=glue, graph=graph)
 
 
+def build_synthetic_hed(device="cuda", seed: int = 1234, fill: bool = True):
+    """ControlNet's HED network (cremage_amd.annotator_hip.ControlNetHED_Apache2, 14.7 M parameters) with name-keyed synthetic weights
+    (prefix "hed."), its five projections scaled by 1 / 16 so that the edge map is not saturated (tests/_hed_cases.fill_ documents the
+    measurement).  fp32 parameters: the only class it runs in."""
+    from .annotator_hip import ControlNetHED_Apache2
+    m = ControlNetHED_Apache2()
+    if fill:
+        synth_fill_(m, seed, prefix="hed.")
+        with torch.no_grad():
+            for k in range(1, 6):
+                proj = getattr(m, f"block{k}").projection
+                proj.weight.mul_(1.0 / 16.0)
+                proj.bias.mul_(1.0 / 16.0)
+    return m.to(device).eval()
+
+
+ANNOTATOR_KINDS = {"hed": "hed", "HED": "hed", "fake_scribble": "fake_scribble", "Fake scribble": "fake_scribble", "scribble": "scribble",
+                   "Scribble": "scribble"}  # ours and the menu names of tools/control_net_annotator.py
+
+
+@torch.no_grad()
+def annotate(image, kind: str, *, image_resolution: int = 512, model=None, glue: str = "host"):
+    """Cremage's ControlNet Annotator tool for its "HED", "Fake scribble" and "Scribble" entries (annotator_wrapper.py generate_hed :190-201,
+    generate_fake_scribble :142-165, generate_scribble :168-187), step by step: the RGB -> BGR flip the wrapper puts in front of every
+    detector - HED is an RGB-input model and still gets BGR, as in the reference -, HWC3, resize_image to `image_resolution`, the detector,
+    and for the fake scribble the host post-processing (nms, blur, thresholds).  image: a PIL image or uint8 [H, W, C] (numpy array or
+    tensor), RGB.  model: the HED network (`build_synthetic_hed` or a loaded ControlNetHED.pth) for "hed" and "fake_scribble".
+    Returns "hed": uint8 [H', W']; "fake_scribble", "scribble": uint8 [H', W', 3].  glue "host" (default): only the network runs on the
+    device, numpy arrays are returned.  glue "device": the image stays on the GPU from the resized bytes to the edge map (ops.hed_fuse);
+    "hed" then returns a uint8 tensor on the device - the same bytes -, the fake scribble's post-processing stays on the host."""
+    from . import postprocess as PP
+    from ._lib import CrgError
+    from .annotator_hip import HEDdetector
+    try:
+        kind = ANNOTATOR_KINDS[kind]
+    except KeyError:
+        raise ValueError(f"unknown annotator {kind!r} (one of {sorted(ANNOTATOR_KINDS)})")
+    glue = _glue(glue)
+    if torch.is_tensor(image):
+        img = image.detach().cpu().numpy()
+    else:
+        img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise ValueError(f"annotate: a uint8 [H, W, C] image expected, got {img.dtype} {img.shape}")
+    if img.ndim == 3:
+        img = img[:, :, ::-1]  # RGB to BGR (:30)
+    img = PP.resize_for_annotator(PP.hwc3(np.ascontiguousarray(img)), image_resolution)
+    if kind == "scribble":
+        return PP.scribble_map(img)
+    if model is None:
+        raise CrgError(f"annotate: {kind!r} needs the HED network (model=)")
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise CrgError(f"annotate: the HED network must live on a HIP device, it is on {dev}")
+    with torch.cuda.device(dev):
+        edge = HEDdetector(model, glue=glue)(np.ascontiguousarray(img))
+    if kind == "hed":
+        return edge
+    if torch.is_tensor(edge):
+        edge = edge.cpu().numpy()
+    return PP.fake_scribble_from_hed(edge)
+
+
+def control_hint(map_u8, batch: int, device) -> torch.Tensor:
+    """A detected map as the control image txt2img(hint=) takes: fp32 [batch, 3, H, W] in [0, 1] - image_generator.py:832-835 without the
+    file round trip (cv2.imread hands back three channels whatever the file holds: HWC3).  map_u8: uint8 [H, W] or [H, W, 3], numpy
+    array or tensor."""
+    from . import postprocess as PP
+    if torch.is_tensor(map_u8):
+        m = map_u8.detach()
+        if m.dtype != torch.uint8 or m.dim() not in (2, 3):
+            raise ValueError(f"control_hint: a uint8 [H, W] or [H, W, 3] map expected, got {m.dtype} {tuple(m.shape)}")
+        if m.dim() == 2:
+            m = m[:, :, None].expand(-1, -1, 3)
+        control = m.to(device).float() / 255.0
+    else:
+        control = torch.from_numpy(PP.hwc3(np.ascontiguousarray(np.asarray(map_u8))).copy()).float().to(device) / 255.0
+    if control.shape[2] != 3:
+        raise ValueError(f"control_hint: three channels expected, got {tuple(control.shape)}")
+    return control[None].expand(int(batch), -1, -1, -1).permute(0, 3, 1, 2).contiguous()
+
+
 def film_schedule(inter_frames: int):
     """The order in which the reference fills the `inter_frames` frames between two given ones, as a list of model calls
     (left slot, right slot, target slot, dt).  Slot k of 0 .. inter_frames + 1 sits at time k / (inter_frames + 1) on an fp32 time axis;

@@ -37,6 +37,11 @@ that a Cremage user finds the whole second-pass chain:
                                    no RANSAC), cv.warpAffine (its fixed-point scheme defined here in integers) and cv.erode, unpinned
                                    against cv2 like the two above.  Host only: their device twins are not built.
 
+  ControlNet annotators            cremage/control_net/annotator_wrapper.py:142-201, annotator/util.py:9-55, annotator/hed/__init__.py:66-96:
+                                   `hwc3`, `annotator_size` and `scribble_map` exact; `resize_for_annotator`, the detector's tail
+                                   (`hed_fuse_host`, the definition of cremage_amd.ops.hed_fuse) and `nms_host` /
+                                   `fake_scribble_from_hed` restate what the reference leaves to cv2 - stated APPROXIMATIONS, unpinned.
+
 Pure Python + PIL + numpy; nothing above the "device twins" section touches the HIP library.
 
 Device twins (`resample_u8_host` and the `*_device` functions): the same arithmetic with the image staying on the GPU.  PIL resizes
@@ -900,6 +905,192 @@ def unblur_faces_device(image_u8_dev: torch.Tensor, landmarks, model: Callable[[
 def colorize_faces_device(image_u8_dev: torch.Tensor, landmarks, model: Callable[[torch.Tensor], torch.Tensor]) -> torch.Tensor:
     """`unblur_faces_device` with the colorize weights in `model` (see `colorize_faces`)."""
     return unblur_faces_device(image_u8_dev, landmarks, model)
+
+
+# ---------------------------------------------------------------------------------------------- ControlNet annotators (HED, scribbles)
+# The host side of tools/control_net_annotator.py's "HED", "Fake scribble" and "Scribble" entries (cremage/control_net/annotator_wrapper.py,
+# annotator/util.py, annotator/hed/__init__.py).  All numpy.  cv2 does not exist in this image: what the reference leaves to cv2 is restated
+# from cv2's documented behaviour and UNPINNED against it; every docstring names those assumptions.  `hed_fuse_host` is also the
+# definition of the device kernel crg_hed_fuse (cremage_amd.ops.hed_fuse), which equals it value for value.
+def hwc3(x: np.ndarray) -> np.ndarray:
+    """annotator/util.py:9-25, exact: uint8 [H, W] / [H, W, 1] -> three equal channels, [H, W, 3] -> itself, [H, W, 4] -> the colour over a
+    white background, color * alpha + 255 * (1 - alpha) in float32, clipped and truncated."""
+    if x.dtype != np.uint8:
+        raise ValueError(f"hwc3: uint8 expected, got {x.dtype}")
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3 or x.shape[2] not in (1, 3, 4):
+        raise ValueError(f"hwc3: [H, W], [H, W, 1], [H, W, 3] or [H, W, 4] expected, got {x.shape}")
+    c = x.shape[2]
+    if c == 3:
+        return x
+    if c == 1:
+        return np.concatenate([x, x, x], axis=2)
+    color = x[:, :, 0:3].astype(np.float32)
+    alpha = x[:, :, 3:4].astype(np.float32) / 255.0
+    y = color * alpha + 255.0 * (1.0 - alpha)
+    return y.clip(0, 255).astype(np.uint8)
+
+
+def annotator_size(h: int, w: int, resolution: int) -> Tuple[int, int, float]:
+    """The size rule of annotator/util.py resize_image (:28-55), exact: k = resolution / min(h, w), each edge scaled by k and rounded to
+    the NEAREST multiple of 64 with np.round (half to even: 96 -> 1.5 -> 2 -> 128, 160 -> 2.5 -> 2 -> 128).  Returns (H, W, k).  An edge
+    below 32 rounds to 0, as in the reference (whose cv2.resize then fails); `resize_for_annotator` raises on it."""
+    hh, ww = float(h), float(w)
+    k = float(resolution) / min(hh, ww)
+    hh *= k
+    ww *= k
+    return int(np.round(hh / 64.0)) * 64, int(np.round(ww / 64.0)) * 64, k
+
+
+def resize_for_annotator(img_u8_hwc: np.ndarray, resolution: int) -> np.ndarray:
+    """resize_image (:28-55): `annotator_size`, then a resample - cv2.INTER_LANCZOS4 for k > 1, cv2.INTER_AREA otherwise.  Stated
+    APPROXIMATION, unpinned against cv2: PIL's LANCZOS (3 lobes, cv2's has 4) for k > 1 and PIL's BOX (the area average cv2's
+    INTER_AREA computes when shrinking) otherwise.  An image already at the size is returned as it is (cv2 copies it)."""
+    from PIL import Image
+    h, w = img_u8_hwc.shape[:2]
+    H, W, k = annotator_size(h, w, resolution)
+    if H < 1 or W < 1:
+        raise ValueError(f"resize_for_annotator: a {h} x {w} image at resolution {resolution} rounds to {H} x {W}")
+    if (H, W) == (h, w):
+        return img_u8_hwc
+    flt = Image.LANCZOS if k > 1 else Image.BOX
+    return np.asarray(Image.fromarray(np.ascontiguousarray(img_u8_hwc)).resize((W, H), flt))
+
+
+def hed_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(index int32 [out], fraction float32 [out]) of one axis of cv2.resize(INTER_LINEAR) on float32 as `hed_fuse_host` assumes it
+    (unpinned): scale = 1.0 / (out / in) in double, f = float32((d + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0 -> (0, 0);
+    s >= in - 1 -> (in - 1, 0).  The double arithmetic exists here only: the device reads these tables."""
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"hed_tables: sizes must be positive (got {in_size} -> {out_size})")
+    scale = 1.0 / (float(out_size) / float(in_size))
+    f = ((np.arange(out_size, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    f = (f - s).astype(np.float32)
+    s = s.astype(np.int64)
+    low, high = s < 0, s >= in_size - 1
+    s = np.where(low, 0, np.where(high, in_size - 1, s))
+    f = np.where(low | high, np.float32(0.0), f).astype(np.float32)
+    return s.astype(np.int32), f
+
+
+def _hed_resize(m: np.ndarray, H: int, W: int) -> np.ndarray:
+    """one fp32 map [.., h, w] -> [.., H, W]: horizontal pass, then vertical on those rows, every operation rounded to fp32"""
+    h, w = m.shape[-2:]
+    if (h, w) == (H, W):
+        return m.copy()
+    sx, fx = hed_tables(w, W)
+    sy, fy = hed_tables(h, H)
+    sx1, sy1 = np.minimum(sx + 1, w - 1), np.minimum(sy + 1, h - 1)
+    one = np.float32(1.0)
+    rows = m[..., sx] * (one - fx) + m[..., sx1] * fx  # [.., h, W]
+    gy, fy = (one - fy)[:, None], fy[:, None]
+    return rows[..., sy, :] * gy + rows[..., sy1, :] * fy
+
+
+def hed_fuse_host(maps: Sequence[np.ndarray], size: Tuple[int, int], return_logit: bool = False):
+    """HEDdetector.__call__'s tail (annotator/hed/__init__.py:73-77): the side maps - float32 [h_i, w_i], or [N, h_i, w_i] for a batch -
+    resized to size = (H, W), averaged, squashed and quantised.  Returns uint8 [H, W] ([N, H, W]), or (bytes, float32 mean field).
+      resize  cv2.resize(INTER_LINEAR) on float32, ASSUMED (unpinned) to be: per axis the `hed_tables` pair (s, f); horizontally
+              r = m[s] * (1 - f) + m[min(s + 1, w - 1)] * f on the two source rows, then the same vertically on those rows; float32, one
+              rounding per operation; a map already at (H, W) is copied
+      mean    np.mean over the stacked maps in float32: ((((u1 + u2) + u3) + u4) + u5) / 5 - assumed to be that order
+      edge    e = 1 / (1 + exp(-float64(mean))), uint8(clip(e * 255.0, 0, 255)) by truncation (:76-77, exact)"""
+    H, W = int(size[0]), int(size[1])
+    if len(maps) < 1:
+        raise ValueError("hed_fuse_host: no side maps")
+    total = None
+    for m in maps:
+        m = np.asarray(m)
+        if m.dtype != np.float32 or m.ndim not in (2, 3):
+            raise ValueError(f"hed_fuse_host: float32 [h, w] or [N, h, w] maps expected, got {m.shape} {m.dtype}")
+        u = _hed_resize(m, H, W)
+        total = u if total is None else total + u
+    mean = (total / np.float32(len(maps))).astype(np.float32)
+    e = 1.0 / (1.0 + np.exp(-mean.astype(np.float64)))
+    edge = (e * 255.0).clip(0, 255).astype(np.uint8)
+    return (edge, mean) if return_logit else edge
+
+
+def _gaussian_taps(sigma: float, ksize: int) -> np.ndarray:
+    """cv2.getGaussianKernel(ksize, sigma) for a computed kernel: exp(-(i - c)^2 / (2 sigma^2)), normalised, in double"""
+    i = np.arange(ksize, dtype=np.float64) - (ksize - 1) / 2.0
+    t = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return t / t.sum()
+
+
+def _blur_reflect101(a: np.ndarray, taps: np.ndarray) -> np.ndarray:
+    """separable correlation of a 2-D array with `taps` along both axes, BORDER_REFLECT_101 (cv2's default), in a's float type"""
+    r = len(taps) // 2
+    for axis in (1, 0):
+        n = a.shape[axis]
+        idx = np.arange(-r, n + r)
+        if n > 1:
+            period = 2 * (n - 1)
+            idx = np.abs(((idx % period) + period) % period)
+            idx = np.where(idx >= n, period - idx, idx)
+        else:
+            idx = np.zeros_like(idx)
+        p = np.take(a, idx, axis=axis)
+        out = np.zeros_like(a)
+        for k, t in enumerate(taps):
+            out = out + np.take(p, np.arange(k, k + n), axis=axis) * a.dtype.type(t)
+        a = out
+    return a
+
+
+def _dilate_line(x: np.ndarray, dy: int, dx: int) -> np.ndarray:
+    """cv2.dilate with a 3-tap line element through the centre in direction (dy, dx); pixels outside the image do not count"""
+    h, w = x.shape
+    p = np.full((h + 2, w + 2), -np.inf, dtype=x.dtype)
+    p[1:-1, 1:-1] = x
+    a = p[1 - dy:1 - dy + h, 1 - dx:1 - dx + w]
+    b = p[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+    return np.maximum(x, np.maximum(a, b))
+
+
+def nms_host(x: np.ndarray, t: float, s: float) -> np.ndarray:
+    """annotator/hed/__init__.py:81-96 on one channel [H, W]: blur with sigma s in float32, keep a pixel's blurred value where it is the
+    maximum of its 3-tap line in any of the four directions (horizontal, vertical, the two diagonals; `dilate(x) == x`, so every pixel
+    of a plateau's interior is kept), 255 where the kept value exceeds t, else 0.  Unpinned assumptions: cv2.GaussianBlur's automatic
+    kernel size on float32 input, round(s * 4 * 2 + 1) | 1 (25 taps at sigma 3), its taps as `_gaussian_taps`, float32 accumulation in
+    tap order, reflect-101 borders; cv2.dilate ignoring what lies outside the image."""
+    xf = np.asarray(x).astype(np.float32)
+    if xf.ndim != 2:
+        raise ValueError(f"nms_host: one channel [H, W] expected, got {xf.shape}")
+    ksize = int(round(s * 4 * 2 + 1)) | 1
+    xf = _blur_reflect101(xf, _gaussian_taps(s, ksize))
+    y = np.zeros_like(xf)
+    for dy, dx in ((0, 1), (1, 0), (1, 1), (1, -1)):
+        np.putmask(y, _dilate_line(xf, dy, dx) == xf, xf)
+    z = np.zeros(y.shape, dtype=np.uint8)
+    z[y > t] = 255
+    return z
+
+
+def fake_scribble_from_hed(edge_u8: np.ndarray) -> np.ndarray:
+    """generate_fake_scribble's post-processing (annotator_wrapper.py:155-163) of the HED map uint8 [H, W]: HWC3, a cv2.resize to the size
+    it already has (a copy), nms(., 127, 3.0), a Gaussian blur of the uint8 result with sigma 3, > 4 -> 255, the rest 0.  Returns uint8
+    [H, W, 3]; the three channels are equal throughout, so one is computed.  Unpinned assumptions: those of `nms_host`; the automatic
+    kernel size on uint8 input, round(3 * 3 * 2 + 1) | 1 = 19 taps; cv2's fixed-point arithmetic on uint8, restated as the float64 sum
+    rounded half to even (at most one level apart, which only matters at the threshold 4)."""
+    edge_u8 = np.asarray(edge_u8)
+    if edge_u8.dtype != np.uint8 or edge_u8.ndim != 2:
+        raise ValueError(f"fake_scribble_from_hed: a uint8 [H, W] edge map expected, got {edge_u8.shape} {edge_u8.dtype}")
+    z = nms_host(edge_u8, 127, 3.0)
+    ksize = int(round(3.0 * 3 * 2 + 1)) | 1
+    b = np.clip(np.rint(_blur_reflect101(z.astype(np.float64), _gaussian_taps(3.0, ksize))), 0, 255).astype(np.uint8)
+    b[b > 4] = 255
+    b[b < 255] = 0
+    return np.repeat(b[:, :, None], 3, axis=2)
+
+
+def scribble_map(img_u8_hwc: np.ndarray) -> np.ndarray:
+    """generate_scribble (annotator_wrapper.py:183-184), exact: 255 in all three channels where the darkest channel is below 127"""
+    out = np.zeros_like(img_u8_hwc, dtype=np.uint8)
+    out[np.min(img_u8_hwc, axis=2) < 127] = 255
+    return out
 
 
 # ---------------------------------------------------------------------------------------------- PNG + generation_data

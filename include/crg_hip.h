@@ -886,6 +886,36 @@ int crg_paste_warped_u8(crg_ctx* ctx, void* stream, void* image, int64_t img_sy,
                         int face_f32, int64_t face_sc, int64_t face_sy, int64_t face_sx, int h, int w, const double* face_from_image, int rect_x,
                         int rect_y, int rect_w, int rect_h);
 
+/* ---- ControlNet's HED annotator (annot.hip; modules/annotator/hed/__init__.py) ----------------------------------------------------------
+ * crg_relu_pool_proj: everything that follows one conv of the VGG trunk, in one pass over the conv's fp32 output x [N][H][W][C] (dense,
+ *   channels-last).  r = x > 0 ? x : 0 (so -0 and NaN give +0); any non-empty subset of
+ *     hi, lo            half-type planes [N][H][W][C]: hi = half(r), lo = half(r - hi), bit-equal to crg_split_bf16 of r
+ *     pool_hi, pool_lo  the same planes of maxpool2x2(r), [N][H/2][W/2][C], stride 2, floor: the last row / column of an odd size is in
+ *                       no window (F.max_pool2d(r, 2, 2))
+ *     proj              fp32 [N][H][W]: proj_bias[0] + sum_c proj_w[c] * r[c] - the block's 1 x 1 `projection` conv; proj_w fp32 [C],
+ *                       proj_bias one fp32 on the device or NULL (0).  Order:
+ *                       per group of 8 consecutive channels acc = fma(w[c], r[c], acc) from 0 in channel order, then the C / 8 group
+ *                       sums - C / 8 a power of two up to 64: an xor butterfly over the group index, offsets 1, 2, ..; otherwise: added
+ *                       in group order - then + proj_bias.  A function of C alone: not of N, H, W, the grid or the batch-invariant mode.
+ *   A pair of planes is both or none.  Every element of x is read exactly once; no atomics, no workspace, no scratch.  C % 8 == 0,
+ *   8 <= C <= 2048; H, W >= 1, both >= 2 with pool planes; x, the planes and proj_w 16-byte aligned; no output may overlap an input or
+ *   another output.
+ *
+ * crg_hed_fuse: HEDdetector's tail (:73-77) in one launch.  maps: HOST array of n_maps (1..8) device pointers to fp32 side maps
+ *   [N][map_h[i]][map_w[i]] (dense; map_h, map_w host arrays, all read when the call is made).  Per output pixel (x, y) and map, with the
+ *   map's tables (sx, fx) = column x and (sy, fy) = row y, every operation rounded to fp32 on its own (no fused multiply-add):
+ *     r(k) = s[k][sx] * (1 - fx) + s[k][min(sx + 1, w - 1)] * fx          for the rows k = sy and min(sy + 1, h - 1)
+ *     u    = r(sy) * (1 - fy) + r(min(sy + 1, h - 1)) * fy                a map whose size is (H, W) is copied, its tables are not read
+ *   mean = (((u_1 + u_2) + u_3) + ..) / (float)n_maps;  e = 1 / (1 + exp(-(double)mean));  out = (uint8) clip(e * 255.0, 0, 255), truncated.
+ *   tab_idx int32 / tab_frac fp32, device: per map W column entries then H row entries, map i at i * (W + H); indices must lie inside
+ *   their map (cremage_amd.postprocess.hed_tables builds them, in double, on the host).  out uint8 [N][H][W]; mean fp32 [N][H][W] or
+ *   NULL.  Errors (-22, before any launch): n_maps outside 1..8, an empty size, an output overlapping a map, the tables or the other output.
+ * No allocation, no host synchronisation.  Profile slot of both: CRG_K_ELEMENTWISE. */
+int crg_relu_pool_proj(crg_ctx* ctx, void* stream, const float* x, void* hi, void* lo, void* pool_hi, void* pool_lo, const float* proj_w,
+                       const float* proj_bias, float* proj, int N, int H, int W, int C);
+int crg_hed_fuse(crg_ctx* ctx, void* stream, int n_maps, const void* const* maps, const int* map_h, const int* map_w, const int* tab_idx,
+                 const float* tab_frac, void* out, float* mean, int N, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif
